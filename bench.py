@@ -8,8 +8,14 @@ fp32): spherical projection of the 2B raw scans, per-pixel normals from the proj
 quaternion -> T, exact nearest-neighbour correspondences, the fused point-to-plane/plane-to-plane loss, backward
 through loss and CNN, gradient all-reduce (N>1) and the Adam update.  Inputs (raw scan point lists) are resident in
 HBM when the timed region starts; the timed steps ROTATE over `--rotate` distinct batches (ragged scan lengths) so
-that no step finds the previous step's intermediates of the same data in a cache.  Rank 0 prints ONE JSON line
-(contract in the task statement) that also carries
+that no step finds the previous step's intermediates of the same data in a cache.  Rank 0 prints ONE JSON line with the
+headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+
+A plain run does only what that line needs: set-up, priming, W warm-up steps, the K timed steps, the line.  With
+`--dump-outputs DIR` it also writes what the last timed step computed (poses, losses, a fixed sample of the updated weights and
+of their gradients) as DIR/<name>.npy, float32 / float64; the inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds every other measurement, each in passes of its own after the timed steps; its line also carries
   "roofline":     the dominant kernel, k_wino_conv (fused Winograd F(2x2,3x3) on the fp32 matrix cores; 36 % of the step):
                   multiply-adds issued / its duration, measured in the timed steps themselves (begin/end timestamps on HIP
                   events attached to every launch), vs the 157.3 TFLOP/s fp32 MFMA peak
@@ -20,7 +26,9 @@ that no step finds the previous step's intermediates of the same data in a cache
   "feed":         the same steps fed from pinned host memory through DataLoader + DevicePrefetcher (H2D in the loop)
   "cpu_baseline": the reference-like step (stored normal lists, B=1) evaluated by the CPU oracle on a bounded sample;
   "cpu_baseline_online_normals": the GPU workload itself (normals computed in the step) on the CPU
-  "kernels":      per-launch HIP-event times and achieved bandwidth of every geometry kernel (back-to-back launches).
+  "kernels":      per-launch HIP-event times and achieved bandwidth of every geometry kernel (back-to-back launches)
+  "autocast", "feed_disk", "shipped_image", "untrained_network", "shipped_config", "ddp_rank": the other legs (see parse())
+  "ddp_timeline": N>1, the gradient all-reduce per bucket in a pass of its own.
 """
 import argparse
 import json
@@ -79,7 +87,50 @@ def parse(argv=None):
     ap.add_argument("--cpu-threads", type=int, default=16, help="torch CPU threads of the baseline (more is slower on a 256-thread host: "
                     "the step is a chain of small ops; 128 threads measured 190 s/pair vs ~10 s/pair)")
     ap.add_argument("--kernel-reps", type=int, default=50)
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run every other measurement: rooflines, kernel table, "
+                    "long run, feeds, bf16 and variant legs, default operating point, DDP rank and timeline, CPU baselines (the options above)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed to DIR/<name>.npy")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 18            # elements of the fixed sample of the weights / gradients
+
+
+def dump_sample_indices(n, k=DUMP_SAMPLE, seed=0):
+    """A fixed, seeded, sorted sample of k indices out of n (all of them when n <= k)."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def step_outputs(trainer, ep, T):
+    """What one training step hands its caller, as host arrays: the poses T [B,4,4], the step's loss sums (Trainer.step's
+    epoch_losses, float64), and the same fixed sample of the updated weights and of the gradients the step computed
+    (all parameters flattened in named_parameters order)."""
+    out = {"transformations": T.detach().float().cpu().numpy()}
+    for k, v in ep.items():
+        out["losses_" + k] = np.asarray(v.detach().double().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)
+    params = [p for _, p in trainer.raw_model.named_parameters()]
+    with torch.no_grad():
+        flat_w = torch.cat([p.detach().reshape(-1).float() for p in params])
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        idx = torch.from_numpy(dump_sample_indices(flat_w.numel())).to(flat_w.device)
+        out["weights_sample"] = flat_w[idx].cpu().numpy()
+        out["gradients_sample"] = flat_g[idx].cpu().numpy()
+    return out
+
+
+def write_outputs(directory, arrays):
+    """DIR/<name>.npy for every array, float32 stays float32, anything else becomes float64; refuses more than DUMP_MAX_BYTES."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the limit of {DUMP_MAX_BYTES}")
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def build_config(args, device):
@@ -1017,6 +1068,7 @@ def main():
     identity_pretrained_state(trainer.raw_model)
     trace("trainer built")
     counter = {"i": 0}
+    last = {}                                                   # the poses of the latest step (--dump-outputs)
     # N > 1: the gradient all-reduce is the path's only exchange; its timeline (per bucket: handed over / completed; the part that is not
     # hidden behind the backward pass) is recorded in a pass of its own AFTER the timed steps (deploy/ddp_trace.py).  The hook is
     # registered now -- DistributedDataParallel takes one hook per model -- and does what the default one does (divide, all-reduce).
@@ -1036,7 +1088,7 @@ def main():
         from delora_amd.deploy.step_geometry import PackedBatch
         if timeline is not None:
             timeline.begin_step()
-        ep, T = trainer.step(preprocessed_dicts=batch if isinstance(batch, PackedBatch) else [dict(s) for s in batch], epoch_losses=ep)
+        ep, last["T"] = trainer.step(preprocessed_dicts=batch if isinstance(batch, PackedBatch) else [dict(s) for s in batch], epoch_losses=ep)
         if timeline is not None:
             timeline.end_step()
         return ep
@@ -1067,12 +1119,13 @@ def main():
                 if batch is None:
                     batch = batches[counter["i"] % len(batches)]
                     counter["i"] += 1
-                return graphed(batch)[0]
+                ep, last["T"] = graphed(batch)
+                return ep
     # in-situ timing of the streaming loss kernel (k_icp_loss) in every timed step: the launch carries a pair of HIP
     # events that receive the kernel's own begin/end timestamps (dl_icp_loss_partial_timed) on the launch stream
     from delora_amd import geometry as G
-    timers = G.LossTimers(reserve=args.steps + 8)
-    loss_timed = (graphed is None or not graphed.captured) and not args.no_profile      # event-carrying launches cannot be captured into a graph
+    timers = G.LossTimers(reserve=args.steps + 8) if args.full else None
+    loss_timed = args.full and (graphed is None or not graphed.captured) and not args.no_profile      # event-carrying launches cannot be captured into a graph
 
     enqueue = {}
 
@@ -1112,7 +1165,7 @@ def main():
     from delora_amd import _lib
     conv_prof = None
     dominant = "k_convh" if args.amp else "k_wino_conv"          # the family with the largest share of the step (conv_profile below)
-    can_profile = (graphed is None or not graphed.captured) and "hip trunk" in cnn_impl_in_use(trainer, args) and not args.no_profile
+    can_profile = args.full and (graphed is None or not graphed.captured) and "hip trunk" in cnn_impl_in_use(trainer, args) and not args.no_profile
     # An event-carrying launch (hipExtLaunchKernelGGL with start/stop events) costs the HOST ~0.25 ms, and it keeps the host from
     # running ahead of the GPU.  With the 26 + 1 such launches in EVERY timed step the 14.7 ms fp32 step of a fresh box was host-bound
     # (492 pairs/s against 545 with --no-profile, same box, back to back).  The timed region therefore carries events in every
@@ -1139,6 +1192,9 @@ def main():
     host_enqueue_ms = enqueue["ms_per_step"]
     rank_ms = enqueue.get("rank_ms_per_step")
     trace("timed region done")
+    if args.dump_outputs and rank == 0:                 # before any further step changes the weights
+        write_outputs(args.dump_outputs, step_outputs(trainer, ep, last["T"]))
+        trace("outputs written")
     roofline_pass = f"every {EVENT_EVERY}th of the K timed steps ({evented['steps']} steps)"
     if not in_timed and (can_profile or loss_timed):
         counter["i"] = 0
@@ -1150,7 +1206,7 @@ def main():
         conv_prof, untimed = _lib.profile_end()
         assert untimed == 0, f"{untimed} launches were not timed: raise the profile capacity"
     ddp_timeline = None
-    if timeline is not None:
+    if timeline is not None and args.full:
         timeline.enabled = True
         n_tl = max(4, min(16, args.steps))
         timed_region(n_tl, run_step)
@@ -1189,7 +1245,7 @@ def main():
         "rank_ms_per_step": ({"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms} if rank_ms else None),
         "ddp_timeline": ddp_timeline,
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         rows, counts = kernel_table(trainer, batches[0], args.kernel_reps)
         if timers.used == 0 and world == 1:                    # graph mode: measure the same launch right after the timed region
             # (one process only: under DDP a training step is a collective -- rank 0 stepping alone would wait for the others forever)
@@ -1318,6 +1374,7 @@ def main():
                     result["ddp_rank"] = {"error": f"{type(e).__name__}: {e}"}
             if not args.no_cpu_baseline:
                 result["cpu_baseline"], result["cpu_baseline_online_normals"] = cpu_baseline(args, cfg)
+    if rank == 0:
         os.write(json_fd, (json.dumps(result) + "\n").encode())
     trace("at the final barrier")
     if world > 1:

@@ -212,3 +212,29 @@ def test_convergence_seeds_study_intervals_overlap():
                 assert abs(ma - mb) <= cells[a][key]["sd"] + cells[b][key]["sd"] + slack * max(ma, mb), (a, b, key, ma, mb)
     for r in d["runs"]:
         assert r["t_rel_percent"] < r["yardstick_no_motion_percent"] / 5.0 and r["final_loss"] < 0.9 * r["first_loss"], r
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    """A plain `bench.py` run measures the headline only; `--full` asks for every other leg; `--dump-outputs` names a directory."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_are_float_files_under_the_size_limit(tmp_path):
+    """write_outputs: DIR/<name>.npy, float32 kept, everything else float64; more than 64 MB in all is refused.  The weight / gradient
+    sample is a fixed, sorted set of distinct indices (the same in every run), all indices when there are fewer than the sample size."""
+    import numpy as np
+    import bench
+    names = bench.write_outputs(str(tmp_path / "d"), {"a": np.ones((2, 4, 4), np.float32), "b": np.arange(3), "c": 1.5})
+    assert names == ["a", "b", "c"]
+    a, b, c = (np.load(tmp_path / "d" / f"{n}.npy") for n in names)
+    assert a.dtype == np.float32 and a.shape == (2, 4, 4) and b.dtype == np.float64 and b.tolist() == [0.0, 1.0, 2.0] and c.dtype == np.float64
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / "e"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / "e").exists()
+    i1, i2 = bench.dump_sample_indices(12_000_000), bench.dump_sample_indices(12_000_000)
+    assert np.array_equal(i1, i2) and len(i1) == bench.DUMP_SAMPLE and np.all(np.diff(i1) > 0) and 0 <= i1[0] and i1[-1] < 12_000_000
+    assert np.array_equal(bench.dump_sample_indices(10), np.arange(10))

@@ -5,7 +5,8 @@ against the CPU oracle and a plain torch fp32 evaluation of the network on the h
   config 0  64x1024, batch 1                         test_config0_64x1024_batch1_step_against_oracle
   config 1  64x2048, batch 8 (bench.py's workload)   test_config1_bench_workload_step_against_oracle,
                                                      test_config1_full_model_gradients_against_cpu_reference,
-                                                     test_bench_final_loss_reproduces
+                                                     test_bench_final_loss_reproduces,
+                                                     test_bench_plain_run_reports_the_headline_and_dumps_the_last_step
   config 3  128x2048, batch 8 per GPU                test_config3_128x2048_batch8_step_against_oracle
   config 4  mixed sensors in one batch               test_config4_mixed_sensor_batch_against_oracle (fp32 and autocast)
 
@@ -289,7 +290,7 @@ def test_bench_final_loss_reproduces():
         ep, _ = _one_step(trainer, batches[i])
     mine = float(ep["loss_epoch"])
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "0", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "0", "--no-cpu-baseline",
                         "--kernel-reps", "2", "--feed-steps", "0", "--long-steps", "0", "--no-live-pmc", "--variant-steps", "2",
                         "--autocast-steps", "0", "--shipped-steps", "8", "--ddp-steps", "2"], capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -323,6 +324,47 @@ def test_bench_final_loss_reproduces():
     assert "error" not in dd, dd
     for prec in ("fp32", "bf16"):
         assert dd[prec]["ddp"]["ms_per_step"] > 0 and np.isfinite(dd[prec]["ddp"]["final_loss"]) and isinstance(dd[prec]["ddp_host_bound"], bool)
+
+
+def test_bench_plain_run_reports_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain `python bench.py` (3 steps, no warm-up) prints the headline line only, and `--dump-outputs` holds what the last of its
+    timed steps computed: the poses, the loss sums, the fixed sample of the updated weights and of their gradients -- the arrays this
+    process computes for the same three steps of the same workload."""
+    import bench
+    dev = _dev()
+    args, cfg, batches, trainer = _bench_setup(8, dev, rotate=8)
+    for b in batches:                      # bench.py primes the allocator with one step per distinct batch before warm-up and timing
+        _one_step(trainer, b)
+    for i in range(3):
+        ep, T = _one_step(trainer, batches[i])
+    mine = bench.step_outputs(trainer, ep, T)
+    del trainer
+    torch.cuda.empty_cache()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "0", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 0 and j["unit"] == "scan-pairs/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert j["ms_per_step"] > 0 and j["value"] == pytest.approx(8 * 1e3 / j["ms_per_step"], rel=1e-3)
+    assert not {"roofline", "roofline_loss", "kernels", "long_run", "feed", "autocast", "cpu_baseline", "shipped_config", "ddp_rank"} & set(j)
+    files = sorted(p.name for p in out.iterdir())
+    assert files == sorted(k + ".npy" for k in mine)
+    got = {k: np.load(out / (k + ".npy")) for k in mine}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values()) and sum(v.nbytes for v in got.values()) <= bench.DUMP_MAX_BYTES
+    assert got["transformations"].shape == (8, 4, 4) and got["weights_sample"].shape == (bench.DUMP_SAMPLE,)
+    assert abs(float(got["losses_loss_epoch"][0]) - j["final_loss"]) <= 1e-6 * abs(j["final_loss"])
+    util.measured("bench.py --dump-outputs poses vs the same 3 steps in-process (relative to the largest element)",
+                  float(np.abs(got["transformations"] - mine["transformations"]).max() / np.abs(mine["transformations"]).max()), bound=REL)
+    for k in (k for k in mine if k.startswith("losses_")):
+        util.measured(f"bench.py --dump-outputs {k} vs in-process (relative)",
+                      float(np.abs(got[k] - mine[k]).max() / max(float(np.abs(mine[k]).max()), 1e-12)), bound=REL)
+    for k, bound in (("weights_sample", 1e-3), ("gradients_sample", 1e-2)):
+        util.measured(f"bench.py --dump-outputs {k} vs in-process (relative norm of the difference)",
+                      float(np.linalg.norm(got[k] - mine[k]) / np.linalg.norm(mine[k])), bound=bound)
 
 
 def test_bench_measures_the_convolution_traffic_itself():
@@ -408,7 +450,7 @@ def test_bench_eight_ranks_dry_run_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DELORA_BENCH_SHARE_GPU="1", DELORA_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", "1", "--width", "256",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "8", "--steps", "3", "--warmup", "1", "--batch", "1", "--width", "256",
            "--rotate", "2", "--kernel-reps", "2", "--no-live-pmc", "--no-profile"]
     # (a bounded wait: eight processes time-slicing one GPU are slow, not stuck -- but a stuck run must cost minutes, not the session)
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=root, start_new_session=True)
@@ -449,7 +491,7 @@ def test_rccl_two_gpus_bench_and_timeline():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DELORA_BENCH_SHARE_GPU", "DELORA_BENCH_BACKEND"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3", "--kernel-reps", "2", "--no-live-pmc", "--no-profile"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "10", "--warmup", "3", "--kernel-reps", "2", "--no-live-pmc", "--no-profile"]
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=root, start_new_session=True)
     try:
         out, err = proc.communicate(timeout=900)
@@ -480,7 +522,7 @@ def test_bench_two_ranks_on_one_gpu_through_torchrun(launcher):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DELORA_BENCH_SHARE_GPU="1", DELORA_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
-    bench_args = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2",
+    bench_args = [os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2",
                   "--rotate", "2", "--kernel-reps", "2", "--no-live-pmc"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
