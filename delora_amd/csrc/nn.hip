@@ -506,7 +506,9 @@ __device__ __forceinline__ float box_lower(const float4 lo, const float4 hi, flo
 // validity tests (a lane without a pixel carries zeros, an empty pixel is zeros) sit BEHIND the screen: an empty pixel is the point
 // (0,0,0), which fails the screen unless the origin is nearer than the lane's best.  The common path is seven vector and two scalar
 // instructions (compare, s_and_saveexec, s_cbranch_execz) -- a SIMD issues scalar instructions at the rate of vector ones, and a
-// wave-uniform "does any lane pass?" test in front of the branch cost six more of them (profiles/r06_nn_lab.txt).
+// wave-uniform "does any lane pass?" test in front of the branch cost six more of them (profiles/r06_nn_lab.txt).  Every walk
+// starts from pass A's candidate (lbest, lidx) -- index included, lidx = -1 only with lbest = 1e300 -- so that an exact tie goes to
+// the lower pixel index whichever member of it pass A happened to see.
 __device__ __forceinline__ void nn_consider(const float4 c, const int p, const float qx, const float qy, const float qz, float& thr,
                                             double& lbest, int& lidx) {
   const float dx = qx - c.x, dy = qy - c.y, dz = qz - c.z;
@@ -514,7 +516,7 @@ __device__ __forceinline__ void nn_consider(const float4 c, const int p, const f
     NN_STAT(13, 1);
     if (p >= 0 && ((__float_as_uint(c.x) | __float_as_uint(c.y) | __float_as_uint(c.z)) << 1) != 0u) {
       const double d2 = dist2(qx, qy, qz, c.x, c.y, c.z);
-      if (d2 < lbest || (d2 == lbest && lidx >= 0 && p < lidx)) {
+      if (d2 < lbest || (d2 == lbest && p < lidx)) {
         lbest = d2; lidx = p;
         thr = (float)lbest * (1.0f + 1e-5f);
       }
@@ -535,7 +537,7 @@ __device__ __forceinline__ void scan_tiles(const Window& w, const float4* __rest
   if (w.nc >= W || ntc >= ntc_all || ((W % NN_TC) != 0 && w.c0 + w.nc > W)) { tc0 = 0; ntc = ntc_all; }
   const int ntiles = (tr1 - tr0 + 1) * ntc;
   double lbest = best;
-  int lidx = -1;
+  int lidx = bidx;                                                          // ties: against pass A's candidate, not past it
   float thr = best < 1e30 ? (float)best * (1.0f + 1e-5f) : 3.0e38f;       // fp32 screen of squared distances
   float dcur = best < 1e30 ? sqrtf((float)best) * (1.0f + 1e-6f) : 3.0e38f;   // wave-uniform cull distance
   const float inv = 1.0f / (float)ntc;
@@ -652,7 +654,7 @@ __device__ __forceinline__ void pyramid_walk(const float4* __restrict__ super_b,
   const int ntr = (H + NN_TR - 1) / NN_TR, ntc = (W + NN_TC - 1) / NN_TC;
   const int nsr = (ntr + NN_SR - 1) / NN_SR, nsc = (ntc + NN_SC - 1) / NN_SC, nsuper = nsr * nsc;
   double lbest = best;
-  int lidx = -1;
+  int lidx = bidx;
   float thr = best < 1e30 ? (float)best * (1.0f + 1e-5f) : 3.0e38f;            // fp32 screen of squared distances
   float dcur = best < 1e30 ? sqrtf((float)best) * (1.0f + 1e-6f) : 3.0e38f;    // wave-uniform cull distance (an upper bound of the answer)
   float lb2[NN_SUPER_TRIPS];
@@ -807,7 +809,7 @@ __device__ __forceinline__ void nn_scan16(const int vblock, const int vgrid, con
     const float qx = rec.qx, qy = rec.qy, qz = rec.qz;
     const float4* tp = tgt + (size_t)b * tgt_ss4;
     double lbest = rec.d2;
-    int lidx = -1;
+    int lidx = rec.idx;
     float thr = lbest < 1e30 ? (float)lbest * (1.0f + 1e-5f) : 3.0e38f;
     const int nchunk = (nc + 15) >> 4;
     const int steps = (r1 - r0 + 1) * nchunk;
@@ -884,7 +886,7 @@ __device__ __forceinline__ void nn_hard16(const int vblock, const int vgrid, con
     const int ntiles = live ? (tr1 - tr0 + 1) * ntc : 0;
     NN_STAT16(4, live ? 1 : 0);
     double lbest = rec.d2;
-    int lidx = -1;
+    int lidx = rec.idx;
     float thr = lbest < 1e30 ? (float)lbest * (1.0f + 1e-5f) : 3.0e38f;
     float dcur = lbest < 1e30 ? sqrtf((float)lbest) * (1.0f + 1e-6f) : 3.0e38f;      // row-uniform cull distance
     const float inv = 1.0f / (float)ntc;

@@ -118,11 +118,18 @@ def _packed(t):
     return t, t.stride(0)
 
 
+def nn_workspace_bytes(B, H, W):
+    """Size of the exact search's workspace for B images of H x W pixels."""
+    return int(_lib.load().dl_nn_workspace_bytes(int(B), int(H), int(W)))
+
+
 def nn_correspond(src_image4, src_normals, tgt_packed, tgt_normals_packed, T, sensor, need_without_normals=False,
-                  want_visible=True, want_match=True):
+                  want_visible=True, want_match=True, workspace=None):
     """Exact nearest target pixel of every transformed source point (source planar, target packed ``[B,H,W,4]``).
     Returns (nn_pix [B,H,W] int32, visible [B]|None, match [B,6,H,W]|None): ``match`` holds, per SOURCE pixel, the matched
-    target point (planes 0..2) and normal (planes 3..5) -- the operand stream of icp_loss()."""
+    target point (planes 0..2) and normal (planes 3..5) -- the operand stream of icp_loss().
+    ``workspace``: an optional caller-owned int64 device tensor of at least nn_workspace_bytes(B, H, W) bytes; the search's
+    work lists and their counters are left in it (tests read them to see which regime served a query)."""
     lib = _lib.load()
     _require_cuda(src_image4, tgt_packed, T)
     s, s_ss = _planar(src_image4, 3)
@@ -134,7 +141,12 @@ def nn_correspond(src_image4, src_normals, tgt_packed, tgt_normals_packed, T, se
     nn = torch.empty((B, H, W), dtype=torch.int32, device=s.device)
     match = torch.empty((B, 6, H, W), dtype=torch.float32, device=s.device) if want_match else None
     vis = torch.empty((B,), dtype=torch.int32, device=s.device) if want_visible else None
-    ws = torch.empty((lib.dl_nn_workspace_bytes(B, H, W) // 8 + 1,), dtype=torch.int64, device=s.device)
+    if workspace is None:
+        ws = torch.empty((lib.dl_nn_workspace_bytes(B, H, W) // 8 + 1,), dtype=torch.int64, device=s.device)
+    else:
+        ws = workspace
+        if ws.dtype != torch.int64 or ws.device != s.device or not ws.is_contiguous() or ws.numel() * 8 < lib.dl_nn_workspace_bytes(B, H, W):
+            raise ValueError(f"workspace must be a contiguous int64 tensor on {s.device} of at least nn_workspace_bytes({B}, {H}, {W}) bytes")
     _lib.check(lib.dl_nn_correspond(_ptr(s), s_ss, _ptr(n), n_ss, _ptr(t), t_ss, _ptr(tn), tn_ss, _ptr(Tc), B,
                                     ctypes.byref(sensor.struct), int(bool(need_without_normals)), _ptr(nn),
                                     _ptr(match), _ptr(vis), _ptr(ws), _stream()), "dl_nn_correspond")

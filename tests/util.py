@@ -171,3 +171,140 @@ def portable_full_state(g):
     state = synthetic.portable_state_dict(int(g["state_seed"]), shapes)
     assert synthetic.digest([state[k] for k in shapes]) == str(g["state_sha"]), "portable weights differ from the fixture's"
     return {k: torch.from_numpy(v) for k, v in state.items()}
+
+
+# ------------------------------------------------------------------------------------ scenes with exact distance ties
+# Every coordinate is a multiple of 2^-10 m below 2^12 m in magnitude: a fp32 difference of two of them is exact, so are its
+# square and the sum of three squares in fp64 -- the search kernel's distances and a float64 torch referee are then the SAME
+# numbers, and two targets placed symmetrically about a plane through the query are an exact tie.
+GRID = 2.0 ** -10
+MIRROR_Z = -1.75                 # the mirror plane z = c of the ground family (a ground plane below the sensor)
+TIE_VFOV_DEG = (-40.0, 15.0)     # far enough below the horizon for the reflections to land in the image
+ROOM = (18.0, 11.0)              # half extents of the room in x and y
+
+
+def on_grid(a):
+    return np.round(np.asarray(a, dtype=np.float64) / GRID) * GRID
+
+
+def tie_sensor_fov():
+    return (TIE_VFOV_DEG[0] * np.pi / 180.0, TIE_VFOV_DEG[1] * np.pi / 180.0), kitti_fov()[1]
+
+
+def _room_surfaces(rng, n):
+    """About n points on the room above the ground plane z = MIRROR_Z (walls, boxes, pillars), none on the plane itself."""
+    c, (X, Y) = MIRROR_Z, ROOM
+    z0, z1 = c + 1.0 / 32.0, c + 4.5
+    pts = []
+    nw = int(n * 0.55)
+    s = rng.uniform(-1.0, 1.0, nw)
+    side = rng.integers(0, 4, nw)
+    z = rng.uniform(z0, z1, nw)
+    x = np.where(side < 2, np.where(side == 0, -X, X), s * X)
+    y = np.where(side < 2, s * Y, np.where(side == 2, -Y, Y))
+    pts.append(np.stack([x, y, z]))
+    boxes = [(-9.0, -5.0, 2.0, 1.0, 1.5), (7.5, 4.0, 1.25, 2.5, 0.75), (3.0, -6.5, 0.75, 0.75, 2.25), (-4.0, 6.0, 1.5, 1.0, 1.0),
+             (12.0, -2.0, 1.0, 1.75, 2.5), (-13.5, 3.5, 0.5, 2.0, 0.5)]
+    nb = int(n * 0.3) // len(boxes)
+    for (bx, by, hx, hy, hz) in boxes:
+        f = rng.integers(0, 5, nb)                   # faces -x, +x, -y, +y and the top
+        u, w, v = rng.uniform(-1.0, 1.0, nb), rng.uniform(-1.0, 1.0, nb), rng.uniform(0.0, 1.0, nb)
+        xx = np.where(f == 0, bx - hx, np.where(f == 1, bx + hx, bx + u * hx))
+        yy = np.where(f == 2, by - hy, np.where(f == 3, by + hy, by + w * hy))
+        zz = np.where(f == 4, c + hz, z0 + v * (c + hz - z0))
+        pts.append(np.stack([xx, np.where(f < 2, by + u * hy, yy), zz]))
+    pillars = [(-2.0, -2.5), (5.0, 1.5), (-7.0, 2.0), (10.0, 6.5)]
+    npl = (n - sum(p.shape[1] for p in pts)) // len(pillars)
+    for (px, py) in pillars:
+        a = rng.uniform(-np.pi, np.pi, npl)
+        pts.append(np.stack([px + 0.25 * np.cos(a), py + 0.25 * np.sin(a), rng.uniform(z0, z1, npl)]))
+    return np.concatenate(pts, axis=1)
+
+
+def _pixels(p, H, W, vfov, hfov):
+    """Pixel index (or -1) of fp32 points as the reference projects them, -1 also for points within 0.05 px of a rounding
+    boundary (a GPU evaluation of atan2 may round those the other way)."""
+    s = oracle_sensor(H, W, vfov, hfov)
+    pix, _, _ = reference_pixels(p.astype(np.float32), s)
+    return np.where(ambiguity_mask(p, s, tol=0.05), -1, pix)
+
+
+def mirror_scene(H, W, family="ground", seed=0, n=None):
+    """Target cloud [3,N] fp32 of exact mirror pairs (one pixel each, no two points sharing a pixel in the image of an
+    (H, W) sensor with tie_sensor_fov()).  family "ground": the room and its reflection z -> 2c - z about z = MIRROR_Z;
+    "seam": the room's half y > 0 and its reflection y -> -y (the partners sit on either side of the azimuth seam for queries
+    on y = 0 with x < 0)."""
+    vfov, hfov = tie_sensor_fov()
+    rng = np.random.default_rng(seed)
+    p = on_grid(_room_surfaces(rng, n or 3 * H * W))
+    if family == "ground":
+        m = p.copy()
+        m[2] = 2.0 * MIRROR_Z - p[2]
+    else:
+        p = p[:, p[1] >= 1.0 / 32.0]
+        m = p.copy()
+        m[1] = -p[1]
+    pa, pb = _pixels(p, H, W, vfov, hfov), _pixels(m, H, W, vfov, hfov)
+    keep = (pa >= 0) & (pb >= 0)
+    idx = np.nonzero(keep)[0]
+    # one point per pixel: the first pair wins a pixel, a pair that lost either of its pixels goes entirely
+    for arr in (pa, pb):
+        _, first = np.unique(arr[idx], return_index=True)
+        idx = idx[np.sort(first)]
+    idx = idx[~np.isin(pa[idx], pb[idx]) & ~np.isin(pb[idx], pa[idx])]
+    return np.concatenate([p[:, idx], m[:, idx]], axis=1).astype(np.float32)
+
+
+def ground_sources(H, W, seed=0):
+    """Source cloud [3,M] fp32: ground hits at z = MIRROR_Z exactly (one per pixel below the horizon, inside the room), x and y
+    on the grid."""
+    vfov, hfov = tie_sensor_fov()
+    rng = np.random.default_rng(seed + 1)
+    rows, cols = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    v = rows.reshape(-1) + rng.uniform(-0.3, 0.3, H * W)
+    u = cols.reshape(-1) + rng.uniform(-0.3, 0.3, H * W)
+    el = vfov[0] + v / (H - 1) * (vfov[1] - vfov[0])
+    az = hfov[0] + u / (W - 1) * (hfov[1] - hfov[0])
+    ok = el < -0.02
+    r = MIRROR_Z / np.tan(el[ok])
+    x, y = on_grid(r * np.cos(az[ok])), on_grid(r * np.sin(az[ok]))
+    ins = (np.abs(x) < ROOM[0] - 0.25) & (np.abs(y) < ROOM[1] - 0.25)
+    p = np.stack([x[ins], y[ins], np.full(int(ins.sum()), MIRROR_Z)])
+    return p[:, _pixels(p, H, W, vfov, hfov) >= 0].astype(np.float32)
+
+
+def exact_pose(quarter_turns=0, t=(0.0, 0.0, 0.0), about="z"):
+    """4x4 float32 rigid motion whose rotation entries are 0 / +-1 (a multiple of 90 degrees about z, or about x), t on the grid:
+    the kernel's fmaf chain and a float64 product give the same transformed point, bit for bit."""
+    c, s = [(1, 0), (0, 1), (-1, 0), (0, -1)][quarter_turns % 4]
+    T = np.eye(4)
+    if about == "z":
+        T[:2, :2] = [[c, -s], [s, c]]
+    else:
+        T[1:3, 1:3] = [[c, -s], [s, c]]
+    T[:3, 3] = on_grid(t)
+    return torch.tensor(T, dtype=torch.float32)
+
+
+def nn_referee(q, tgt_pts, tgt_pix, chunk=256):
+    """Nearest target of every query with the tie rule written out: the smallest (d2, pixel index), lexicographically.
+    q [3,M], tgt_pts [3,N] (any float dtype; evaluated in float64 with explicit differences, not the matmul form of cdist),
+    tgt_pix [N] pixel ids.  Returns (pixel [M] int64, d2 [M] float64, ties [M] int64 = targets at that minimum)."""
+    q = q.double()
+    t = tgt_pts.double()
+    pix = tgt_pix.long().to(t.device)
+    big = torch.iinfo(torch.int64).max
+    out_pix, out_d2, out_ties = [], [], []
+    for i in range(0, q.shape[1], chunk):
+        qc = q[:, i:i + chunk, None]
+        dx, dy, dz = qc[0] - t[0][None], qc[1] - t[1][None], qc[2] - t[2][None]
+        d2 = dx * dx + dy * dy + dz * dz
+        m = d2.min(dim=1).values
+        at = d2 == m[:, None]
+        out_pix.append(torch.where(at, pix[None], torch.full_like(d2, 0, dtype=torch.int64) + big).min(dim=1).values)
+        out_d2.append(m)
+        out_ties.append(at.sum(dim=1))
+    if not out_pix:
+        e = torch.zeros(0, dtype=torch.int64, device=t.device)
+        return e, e.double(), e
+    return torch.cat(out_pix), torch.cat(out_d2), torch.cat(out_ties)
