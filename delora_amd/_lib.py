@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdelora_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class DeloraHipError(RuntimeError):
@@ -83,6 +83,12 @@ SIGNATURES = {
     "dl_heads_fwd": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dl_heads_bwd_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "dl_heads_bwd": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dl_heads_fwd_drop": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dl_heads_bwd_drop": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dl_dropout_scale_f32": (_i32, [_vp, _u32, ctypes.c_double, _i64, _vp, _vp]),
+    "dl_stem_input_nhwc_drop_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, ctypes.c_double, _vp, _vp]),
+    "dl_channel_scale_nhwc_t": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "dl_channel_scale_bwd_act_nhwc_t": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_mean_hw_nhwc_h": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_mean_hw_bwd_act_h": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_conv2d_wgrad_h_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),

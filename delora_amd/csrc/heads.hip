@@ -32,7 +32,8 @@ __device__ __forceinline__ float hd_dact(float a, int act) { return act == 1 ? 1
 // re-read it from global memory inside the k loop: 31 us per launch, all of it load latency).
 __global__ __launch_bounds__(256) void k_heads_rows(const float* __restrict__ x, int B, int K, const float* __restrict__ w0, const float* __restrict__ b0,
                                                     const float* __restrict__ w1, const float* __restrict__ b1, int rows, int nmat, int act,
-                                                    int KC, float* __restrict__ y /* [B][nmat][rows] */) {
+                                                    int KC, const float* __restrict__ pre_scale /* [B][rows] or null (nmat == 1) */,
+                                                    float* __restrict__ y /* [B][nmat][rows] */) {
   extern __shared__ float sx[];                             // [B][KC]: a chunk of KC reduction elements of every sample
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int gr = min(blockIdx.x * 4 + wave, rows * nmat - 1);                     // global row over the nmat matrices (surplus waves repeat the last)
@@ -60,7 +61,11 @@ __global__ __launch_bounds__(256) void k_heads_rows(const float* __restrict__ x,
   for (int b = 0; b < HD_MAXB; ++b) {
     if (b < B) {
       const float s = wave_sum(acc[b]);
-      if (lane == 0) y[((size_t)b * nmat + m) * rows + r] = hd_act(s + bias, act);
+      if (lane == 0) {
+        float pre = s + bias;
+        if (pre_scale) pre *= pre_scale[(size_t)b * rows + r];                     // dropout on the fc output (dl_heads_fwd_drop)
+        y[((size_t)b * nmat + m) * rows + r] = hd_act(pre, act);
+      }
     }
   }
 }
@@ -145,7 +150,8 @@ __global__ __launch_bounds__(256) void k_heads_out_bwd(const float* __restrict__
 #define HD_HB_WAVES 8
 __global__ __launch_bounds__(64 * HD_HB_WAVES) void k_heads_hidden_bwd(const float* __restrict__ a1, const float* __restrict__ gh, HeadsP p, int B, int R, int Hd,
                                                                        int act, float* __restrict__ d_r1w, float* __restrict__ d_r1b,
-                                                                       float* __restrict__ d_t1w, float* __restrict__ d_t1b, float* __restrict__ gout) {
+                                                                       float* __restrict__ d_t1w, float* __restrict__ d_t1b,
+                                                                       const float* __restrict__ fc_scale /* [B][R] or null */, float* __restrict__ gout) {
   extern __shared__ float sgh[];             // [B][2 Hd], then [waves][HD_MAXB][64] for the reduction
   float* red = sgh + B * 2 * Hd;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -187,7 +193,9 @@ __global__ __launch_bounds__(64 * HD_HB_WAVES) void k_heads_hidden_bwd(const flo
         float s = 0.f;
 #pragma unroll
         for (int wv_ = 0; wv_ < HD_HB_WAVES; ++wv_) s += red[(wv_ * HD_MAXB + b) * 64 + lane];
-        gout[(size_t)b * R + j] = s * hd_dact(av[b], act);
+        float go = s * hd_dact(av[b], act);
+        if (fc_scale) go *= fc_scale[(size_t)b * R + j];                           // a1 = act(fc_out * fc_scale): the mask's own factor
+        gout[(size_t)b * R + j] = go;
       }
   }
 }
@@ -251,19 +259,31 @@ static HeadsP heads_params(const dl_heads_params* p) {
   return HeadsP{p->fc_w, p->fc_b, p->r1_w, p->r1_b, p->r3_w, p->r3_b, p->t1_w, p->t1_b, p->t3_w, p->t3_b};
 }
 
-/* see include/delora_hip.h */
-extern "C" int dl_heads_fwd(const float* x, const dl_heads_params* params, int32_t B, int32_t F, int32_t R, int32_t Hd, int32_t act,
-                            float* a1, float* a2, float* rot_raw, float* translation, float* rotation, float* norm, dl_stream stream) {
-  if (int rc = heads_check("dl_heads_fwd", x, a1, params, B, F, R, Hd, act)) return rc;
-  if (!a2 || !rot_raw || !translation || !rotation || !norm) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_heads_fwd: null output");
+static int heads_fwd(const char* who, const float* x, const dl_heads_params* params, int B, int F, int R, int Hd, int act, const float* fc_scale,
+                     float* a1, float* a2, float* rot_raw, float* translation, float* rotation, float* norm, dl_stream stream) {
+  if (int rc = heads_check(who, x, a1, params, B, F, R, Hd, act)) return rc;
+  if (!a2 || !rot_raw || !translation || !rotation || !norm) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null output", who);
   const HeadsP p = heads_params(params);
   hipStream_t st = (hipStream_t)stream;
   // the layer input is staged in LDS in chunks of KC reduction elements per sample (at most 48 KB)
   const int kc_f = heads_kc(B, F), kc_r = heads_kc(B, R);
-  hipLaunchKernelGGL(k_heads_rows, dim3((R + 3) / 4), dim3(256), (size_t)B * kc_f * sizeof(float), st, x, B, F, p.fc_w, p.fc_b, (const float*)nullptr, (const float*)nullptr, R, 1, act, kc_f, a1);
-  hipLaunchKernelGGL(k_heads_rows, dim3((2 * Hd + 3) / 4), dim3(256), (size_t)B * kc_r * sizeof(float), st, (const float*)a1, B, R, p.r1_w, p.r1_b, p.t1_w, p.t1_b, Hd, 2, act, kc_r, a2);
+  hipLaunchKernelGGL(k_heads_rows, dim3((R + 3) / 4), dim3(256), (size_t)B * kc_f * sizeof(float), st, x, B, F, p.fc_w, p.fc_b, (const float*)nullptr, (const float*)nullptr, R, 1, act, kc_f, fc_scale, a1);
+  hipLaunchKernelGGL(k_heads_rows, dim3((2 * Hd + 3) / 4), dim3(256), (size_t)B * kc_r * sizeof(float), st, (const float*)a1, B, R, p.r1_w, p.r1_b, p.t1_w, p.t1_b, Hd, 2, act, kc_r, (const float*)nullptr, a2);
   hipLaunchKernelGGL(k_heads_out, dim3(1), dim3(256), 0, st, (const float*)a2, p, B, Hd, rot_raw, translation, rotation, norm);
-  return dl_check_launch("dl_heads_fwd");
+  return dl_check_launch(who);
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_heads_fwd(const float* x, const dl_heads_params* params, int32_t B, int32_t F, int32_t R, int32_t Hd, int32_t act,
+                            float* a1, float* a2, float* rot_raw, float* translation, float* rotation, float* norm, dl_stream stream) {
+  return heads_fwd("dl_heads_fwd", x, params, B, F, R, Hd, act, nullptr, a1, a2, rot_raw, translation, rotation, norm, stream);
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_heads_fwd_drop(const float* x, const dl_heads_params* params, int32_t B, int32_t F, int32_t R, int32_t Hd, int32_t act,
+                                 const float* fc_scale, float* a1, float* a2, float* rot_raw, float* translation, float* rotation, float* norm,
+                                 dl_stream stream) {
+  return heads_fwd("dl_heads_fwd_drop", x, params, B, F, R, Hd, act, fc_scale, a1, a2, rot_raw, translation, rotation, norm, stream);
 }
 
 /* see include/delora_hip.h */
@@ -273,15 +293,14 @@ extern "C" size_t dl_heads_bwd_workspace_bytes(int32_t B, int32_t F, int32_t R, 
   return ((size_t)B * 2 * Hd + (size_t)B * R + chunks * B * F) * sizeof(float);      // gh, gout, per-chunk partial input gradients
 }
 
-/* see include/delora_hip.h */
-extern "C" int dl_heads_bwd(const float* x, const dl_heads_params* params, int32_t B, int32_t F, int32_t R, int32_t Hd, int32_t act,
-                            const float* a1, const float* a2, const float* rot_raw, const float* norm, const float* grad_translation,
-                            const float* grad_rotation, const dl_heads_params* grads, float* grad_x, void* workspace, dl_stream stream) {
-  if (int rc = heads_check("dl_heads_bwd", x, a1, params, B, F, R, Hd, act)) return rc;
-  if (int rc = heads_check("dl_heads_bwd (grads)", x, a1, grads, B, F, R, Hd, act)) return rc;
+static int heads_bwd(const char* who, const float* x, const dl_heads_params* params, int B, int F, int R, int Hd, int act, const float* fc_scale,
+                     const float* a1, const float* a2, const float* rot_raw, const float* norm, const float* grad_translation,
+                     const float* grad_rotation, const dl_heads_params* grads, float* grad_x, void* workspace, dl_stream stream) {
+  if (int rc = heads_check(who, x, a1, params, B, F, R, Hd, act)) return rc;
+  if (int rc = heads_check(who, x, a1, grads, B, F, R, Hd, act)) return rc;
   if (!a2 || !rot_raw || !norm || !grad_translation || !grad_rotation || !grad_x || !workspace)
-    return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_heads_bwd: null pointer argument");
-  if (((size_t)B * 2 * Hd + HD_HB_WAVES * HD_MAXB * 64) * sizeof(float) > 60000) return dl_fail(DL_ERR_UNSUPPORTED, "dl_heads_bwd: hidden layer too wide for the LDS copy");
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
+  if (((size_t)B * 2 * Hd + HD_HB_WAVES * HD_MAXB * 64) * sizeof(float) > 60000) return dl_fail(DL_ERR_UNSUPPORTED, "%s: hidden layer too wide for the LDS copy", who);
   const HeadsP p = heads_params(params);
   float* gh = (float*)workspace;
   float* gout = gh + (size_t)B * 2 * Hd;
@@ -292,9 +311,26 @@ extern "C" int dl_heads_bwd(const float* x, const dl_heads_params* params, int32
                      (float*)grads->r3_w, (float*)grads->r3_b, (float*)grads->t3_w, (float*)grads->t3_b, gh);
   hipLaunchKernelGGL(k_heads_hidden_bwd, dim3((R + 63) / 64), dim3(64 * HD_HB_WAVES), ((size_t)B * 2 * Hd + HD_HB_WAVES * HD_MAXB * 64) * sizeof(float), st, a1,
                      (const float*)gh, p, B, R, Hd, act,
-                     (float*)grads->r1_w, (float*)grads->r1_b, (float*)grads->t1_w, (float*)grads->t1_b, gout);
+                     (float*)grads->r1_w, (float*)grads->r1_b, (float*)grads->t1_w, (float*)grads->t1_b, fc_scale, gout);
   hipLaunchKernelGGL(k_heads_fc_bwd, dim3((F + 255) / 256, chunks), dim3(256), 0, st, x, (const float*)gout, p.fc_w, B, F, R, (float*)grads->fc_w,
                      (float*)grads->fc_b, part);
   hipLaunchKernelGGL(k_heads_gx_reduce, dim3((B * F + 255) / 256), dim3(256), 0, st, (const float*)part, chunks, B * F, grad_x);
-  return dl_check_launch("dl_heads_bwd");
+  return dl_check_launch(who);
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_heads_bwd(const float* x, const dl_heads_params* params, int32_t B, int32_t F, int32_t R, int32_t Hd, int32_t act,
+                            const float* a1, const float* a2, const float* rot_raw, const float* norm, const float* grad_translation,
+                            const float* grad_rotation, const dl_heads_params* grads, float* grad_x, void* workspace, dl_stream stream) {
+  return heads_bwd("dl_heads_bwd", x, params, B, F, R, Hd, act, nullptr, a1, a2, rot_raw, norm, grad_translation, grad_rotation, grads, grad_x,
+                   workspace, stream);
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_heads_bwd_drop(const float* x, const dl_heads_params* params, int32_t B, int32_t F, int32_t R, int32_t Hd, int32_t act,
+                                 const float* fc_scale, const float* a1, const float* a2, const float* rot_raw, const float* norm,
+                                 const float* grad_translation, const float* grad_rotation, const dl_heads_params* grads, float* grad_x,
+                                 void* workspace, dl_stream stream) {
+  return heads_bwd("dl_heads_bwd_drop", x, params, B, F, R, Hd, act, fc_scale, a1, a2, rot_raw, norm, grad_translation, grad_rotation, grads,
+                   grad_x, workspace, stream);
 }

@@ -92,7 +92,9 @@ class FusedHeads(torch.autograd.Function):
     """fc -> the two two-layer heads -> whole-batch quaternion norm as ``dl_heads_fwd`` / ``dl_heads_bwd`` (csrc/heads.hip): three launches
     forward and four backward instead of ~45 small library launches (reference: src/models/resnet_modified.py:118-120 ``fc``,
     src/models/model.py:74-83 the heads, :114 the norm).  ``forward(x [B,F], act, fc.w, fc.b, rot.1.w, rot.1.b, rot.3.w, rot.3.b,
-    tr.1.w, tr.1.b, tr.3.w, tr.3.b) -> (translation [B,3], rotation [B,4])``; fp32 CUDA tensors, B <= 16."""
+    tr.1.w, tr.1.b, tr.3.w, tr.3.b) -> (translation [B,3], rotation [B,4])``; fp32 CUDA tensors, B <= 16.  An optional eleventh
+    tensor ``fc_scale [B,R]`` (0 or 1 / (1 - p): the dropout mask of the fc output, ``ring_conv.dropout_scale``) selects
+    ``dl_heads_fwd_drop`` / ``dl_heads_bwd_drop``: ``a1 = act(fc(x) * fc_scale)``."""
 
     ORDER = ("fc_w", "fc_b", "r1_w", "r1_b", "r3_w", "r3_b", "t1_w", "t1_b", "t3_w", "t3_b")
 
@@ -110,7 +112,8 @@ class FusedHeads(torch.autograd.Function):
         from .. import _lib
         lib = _lib.load()
         x = x.contiguous()
-        params = tuple(p.contiguous() for p in params)
+        fc_scale = params[10].contiguous() if len(params) > 10 else None
+        params = tuple(p.contiguous() for p in params[:10])
         B, F = x.shape
         R, Hd = params[0].shape[0], params[2].shape[0]
         dev = x.device
@@ -125,10 +128,17 @@ class FusedHeads(torch.autograd.Function):
         st = FusedHeads._struct(params)
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         vp = lambda t: ctypes.c_void_p(t.data_ptr())                                  # noqa: E731
-        _lib.check(lib.dl_heads_fwd(vp(x), ctypes.byref(st), B, F, R, Hd, int(act), vp(a1), vp(a2), vp(rot_raw), vp(translation), vp(rotation),
-                                    vp(norm), stream), "dl_heads_fwd")
+        if fc_scale is None:
+            _lib.check(lib.dl_heads_fwd(vp(x), ctypes.byref(st), B, F, R, Hd, int(act), vp(a1), vp(a2), vp(rot_raw), vp(translation), vp(rotation),
+                                        vp(norm), stream), "dl_heads_fwd")
+        else:
+            if tuple(fc_scale.shape) != (B, R) or fc_scale.dtype != torch.float32:
+                raise ValueError(f"fc_scale must be fp32 [{B},{R}], got {tuple(fc_scale.shape)} {fc_scale.dtype}")
+            _lib.check(lib.dl_heads_fwd_drop(vp(x), ctypes.byref(st), B, F, R, Hd, int(act), vp(fc_scale), vp(a1), vp(a2), vp(rot_raw),
+                                             vp(translation), vp(rotation), vp(norm), stream), "dl_heads_fwd_drop")
         ctx.act = int(act)
-        ctx.save_for_backward(x, a1, a2, small, *params)
+        ctx.has_scale = fc_scale is not None
+        ctx.save_for_backward(x, a1, a2, small, *params, *([fc_scale] if fc_scale is not None else []))
         return translation, rotation
 
     @staticmethod
@@ -137,6 +147,7 @@ class FusedHeads(torch.autograd.Function):
         from .. import _lib
         lib = _lib.load()
         x, a1, a2, small, *params = ctx.saved_tensors
+        fc_scale = params.pop() if ctx.has_scale else None
         B, F = x.shape
         R, Hd = params[0].shape[0], params[2].shape[0]
         rot_raw, norm = small[:4 * B], small[4 * B:]
@@ -149,6 +160,10 @@ class FusedHeads(torch.autograd.Function):
         st, gs = FusedHeads._struct(params), FusedHeads._struct(grads)
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         vp = lambda t: ctypes.c_void_p(t.data_ptr())                                  # noqa: E731
-        _lib.check(lib.dl_heads_bwd(vp(x), ctypes.byref(st), B, F, R, Hd, ctx.act, vp(a1), vp(a2), vp(rot_raw), vp(norm), vp(gt), vp(gr),
-                                    ctypes.byref(gs), vp(gx), vp(ws), stream), "dl_heads_bwd")
-        return (gx, None, *grads)
+        if fc_scale is None:
+            _lib.check(lib.dl_heads_bwd(vp(x), ctypes.byref(st), B, F, R, Hd, ctx.act, vp(a1), vp(a2), vp(rot_raw), vp(norm), vp(gt), vp(gr),
+                                        ctypes.byref(gs), vp(gx), vp(ws), stream), "dl_heads_bwd")
+            return (gx, None, *grads)
+        _lib.check(lib.dl_heads_bwd_drop(vp(x), ctypes.byref(st), B, F, R, Hd, ctx.act, vp(fc_scale), vp(a1), vp(a2), vp(rot_raw), vp(norm), vp(gt),
+                                         vp(gr), ctypes.byref(gs), vp(gx), vp(ws), stream), "dl_heads_bwd_drop")
+        return (gx, None, *grads, None)

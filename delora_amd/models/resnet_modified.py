@@ -11,8 +11,10 @@ Two GPU paths compute it (``cnn_impl``; both are compared with each other and wi
     for layer1..layer4 (fused Winograd / direct MFMA convolutions with the wrap-around as addressing and the elementwise tail
     in their epilogues; one Function in a single process, cut per layer under DDP so that the gradient all-reduce overlaps
     the backward) and ``MeanHW`` before ``fc``; inside ``torch.autocast`` the same structure in bf16 / fp16
-    (``RingSegmentH``: csrc/convh.hip, wgradh.hip);
-  * everything else (narrow test networks, autocast, dropout): the modules below -- library convolutions on inputs that
+    (``RingSegmentH``: csrc/convh.hip, wgradh.hip).  ``use_dropout`` in training mode stays on this path: the input mask is applied
+    inside the stem's transposing copy, the channel mask by ``ring_conv.ChannelDropout`` at an extra cut in front of layer4, the
+    fc mask inside the fused heads (csrc/dropout.hip: a counter-based stream of the library's own, seeded per forward pass);
+  * everything else (narrow test networks, autocast shapes that do not tile, ``cnn_impl: modules``): the modules below -- library convolutions on inputs that
     travel in wrapped form, with activation (+ residual add) and the wrap-around padding as ONE fused HIP elementwise op
     (``ring_ops.ring_act_pad``) instead of the reference's separate tanh, add and three-copy F.pad per layer, and the
     stem's activation + padding + max-pooling + padding as one more (``ring_ops.ring_act_pool_pad``).
@@ -70,6 +72,7 @@ class ResNetModified(torch.nn.Module):
         # otherwise; "modules" forces the latter, "hip" makes unsupported shapes an error.
         self.impl = impl
         self.use_dropout = bool(use_dropout)
+        self.dropout_p = 0.2                           # the reference's rate at all three sites (resnet_modified.py:33-38)
         widths = [int(c / factor_fewer_resnet_channels) for c in (64, 128, 256, 512)]
         self.inplanes = widths[0]
         self.dropout_values = torch.nn.Dropout(p=0.2) if use_dropout else torch.nn.Identity()
@@ -119,15 +122,16 @@ class ResNetModified(torch.nn.Module):
 
     def _note_module_path(self, x):
         """One line per (shape, dtype, mode) whenever a CUDA input takes the module path (library convolutions + ring ops) instead of
-        the HIP stem + trunk: a 5x slower path must not be taken silently (narrow test networks, dropout, widths not divisible by 4)."""
+        the HIP stem + trunk: a 5x slower path must not be taken silently (narrow test networks, widths not divisible by 4)."""
         if not x.is_cuda or self.impl == "modules":
             return
         key = (tuple(x.shape), x.dtype, torch.is_autocast_enabled(), self.training and self.use_dropout)
         seen = self.__dict__.setdefault("_module_path_noted", set())
         if key not in seen:
             seen.add(key)
-            why = ("dropout is active" if key[3] else "autocast shapes do not tile (csrc/convh.hip)" if key[2]
-                   else "channel counts are not multiples of 64, or the width is not a multiple of 4")
+            why = ("autocast shapes do not tile (csrc/convh.hip)" if key[2]
+                   else "channel counts are not multiples of 64, or the width is not a multiple of 4"
+                   + (" (active dropout needs the HIP stem as well as the trunk)" if key[3] else ""))
             print(f"[delora_amd] CNN input {key[0]} {str(x.dtype).replace('torch.', '')} runs on the MODULE path (library convolutions), "
                   f"not on the HIP stem + trunk: {why}", flush=True)
 
@@ -142,19 +146,15 @@ class ResNetModified(torch.nn.Module):
                 and ring_conv.supported((batch, H, W // 4, C0), self._trunk_blocks()[0]))
 
     def hip_trunk_applicable(self, x_pooled_shape_nhwc, x):
-        """The HIP trunk runs fp32 CUDA tensors, no dropout, outside autocast, on shapes that tile."""
+        """The HIP trunk runs fp32 CUDA tensors outside autocast on shapes that tile (with or without dropout)."""
         if self.impl == "modules" or not x.is_cuda or x.dtype != torch.float32 or torch.is_autocast_enabled():
-            return False
-        if self.use_dropout and self.training:
             return False
         return ring_conv.supported(x_pooled_shape_nhwc, self._trunk_blocks()[0])
 
     def hip_half_applicable(self, x):
-        """The half-precision HIP trunk (``ring_conv.RingTrunkH``) runs CUDA inputs inside ``torch.autocast`` (fp16 / bf16), no
-        dropout, on shapes that tile; returns the autocast dtype or None."""
+        """The half-precision HIP trunk (``ring_conv.RingTrunkH``) runs CUDA inputs inside ``torch.autocast`` (fp16 / bf16) on shapes
+        that tile (with or without dropout); returns the autocast dtype or None."""
         if self.impl == "modules" or not x.is_cuda or not torch.is_autocast_enabled():
-            return None
-        if self.use_dropout and self.training:
             return None
         dtype = torch.get_autocast_dtype("cuda")
         N, Cin, Hin, Win = x.shape
@@ -163,9 +163,32 @@ class ResNetModified(torch.nn.Module):
             return None
         return dtype if ring_conv.supported_h((N, Hin, Win // 4, C0), self._trunk_blocks()[0]) else None
 
+    def dropout_active(self):
+        return self.use_dropout and self.training
+
+    def _draw_dropout(self, x, c3):
+        """Seed and the two small masks of one forward pass (kept in ``last_dropout`` for inspection; under a captured graph these are
+        the static tensors every replay overwrites): (stem argument, trunk argument, fc scale)."""
+        N = x.shape[0]
+        rank, world = 0, 1
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+        seed = ring_conv.mix_rank(ring_conv.draw_seed(x.device), rank, world)
+        p = float(self.dropout_p)
+        channels = ring_conv.dropout_scale(seed, ring_conv.SITE_CHANNELS, p, N * c3).view(N, c3)
+        fc = ring_conv.dropout_scale(seed, ring_conv.SITE_FC, p, N * self.fc.out_features).view(N, self.fc.out_features)
+        self.last_dropout = {"seed": seed, "p": p, "channels": channels, "fc": fc}
+        return (seed, p), (channels, len(self.layer1) + len(self.layer2) + len(self.layer3)), fc
+
     def pooled_features(self, x):
         """The globally pooled feature ``[N,C']`` (fp32; the input of ``fc``) when the whole CNN runs on the HIP stem + trunk -- fp32, or
         half precision inside autocast -- else None.  Returns (feat, last feature map as NCHW view or None)."""
+        return self.pooled_features_drop(x)[:2]
+
+    def pooled_features_drop(self, x):
+        """``pooled_features`` plus the third element the heads need when dropout is active: the scale ``[N,R]`` (0 or 1 / (1 - p)) to
+        apply to the fc output, else None.  With active dropout one seed is drawn per call -- only once the HIP path is known to take
+        the input -- and serves the three sites."""
         act = "relu" if self.activation_fct == "relu" else "tanh"
         N, Cin, Hin, Win = x.shape
         C0 = self.conv1.out_channels
@@ -174,37 +197,48 @@ class ResNetModified(torch.nn.Module):
             # autocast: fp32 stem (8 input channels: 0.4 ms), then layer1..layer4 + pooling on the half-precision MFMA kernels
             blocks, weights = self._trunk_blocks()
             with torch.autocast("cuda", enabled=False):
+                if self.dropout_active():
+                    d_in, d_ch, fc_scale = self._draw_dropout(x, self.layer3[-1].conv2.out_channels)
+                    x0 = ring_conv.RingStem.apply(x.float(), self.conv1.weight, ring_conv.ACT[act], d_in)
+                    return ring_conv.ring_trunk_h(x0, ring_conv.ACT[act], blocks, half, weights, channel_drop=d_ch), None, fc_scale
                 x0 = ring_conv.RingStem.apply(x.float(), self.conv1.weight, ring_conv.ACT[act])          # [N,H,W/4,C0] fp32
                 feat = ring_conv.RingTrunkH.apply(x0, ring_conv.ACT[act], blocks, half, *weights)     # [N,C'] fp32
-            return feat, None
+            return feat, None, None
         if (self.hip_trunk_applicable((N, Hin, Win // 4, C0), x) and Win % 4 == 0
                 and ring_conv.stem_supported(tuple(x.shape), C0)):
             # channels-last from the first layer on: stem (conv1 + act + pool) and layer1..layer4 on the HIP kernels
             blocks, weights = self._trunk_blocks()
+            if self.dropout_active():
+                d_in, d_ch, fc_scale = self._draw_dropout(x, self.layer3[-1].conv2.out_channels)
+                x0 = ring_conv.RingStem.apply(x, self.conv1.weight, ring_conv.ACT[act], d_in)
+                x4 = ring_conv.ring_trunk(x0, ring_conv.ACT[act], blocks, weights, channel_drop=d_ch)
+                return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), fc_scale
             x0 = ring_conv.RingStem.apply(x, self.conv1.weight, ring_conv.ACT[act])              # [N,H,W/4,C0]
             x4 = ring_conv.RingTrunk.apply(x0, ring_conv.ACT[act], blocks, *weights)          # [N,H',W',C']
-            return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2)
-        return None, None
+            return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), None
+        return None, None, None
 
     def forward(self, x):
         act = "relu" if self.activation_fct == "relu" else "tanh"
-        x = self.dropout_values(x)
         N, Cin, Hin, Win = x.shape
         C0 = self.conv1.out_channels
-        feat, x4 = self.pooled_features(x)
+        feat, x4, fc_scale = self.pooled_features_drop(x)          # (the HIP path applies the input and channel dropout itself)
         if feat is not None:
             with torch.autocast("cuda", enabled=False):
-                out = self.dropout_values(self.fc(feat))
+                out = self.fc(feat)
+                if fc_scale is not None:
+                    out = out * fc_scale                            # the same mask the fused heads would apply
             return [None, None, None, x4, out]
+        x = self.dropout_values(x)
         p = ring_act_pad(x, "none", pad=True)
         p = ring_act_pool_pad(self.conv1(p), act)                    # act + wrap + self.maxpool + wrap, fused
         N, C0, H0, Wp = p.shape
-        if self.hip_trunk_applicable((N, H0, Wp - 2, C0), p):
+        if not self.dropout_active() and self.hip_trunk_applicable((N, H0, Wp - 2, C0), p):
             # channels-last trunk: layer1..layer4 as one autograd Function on the fp32 matrix cores
             blocks, weights = self._trunk_blocks()
             x0 = p[..., 1:-1].permute(0, 2, 3, 1).contiguous()
             x4 = ring_conv.RingTrunk.apply(x0, ring_conv.ACT[act], blocks, *weights)          # [N,H',W',C']
-            out = self.dropout_values(self.fc(ring_conv.MeanHW.apply(x4)))
+            out = self.fc(ring_conv.MeanHW.apply(x4))
             return [None, None, None, x4.permute(0, 3, 1, 2), out]
         if self.impl == "hip":
             raise RuntimeError(f"cnn_impl 'hip': the HIP trunk does not support input {tuple(x.shape)} / dtype {x.dtype}")

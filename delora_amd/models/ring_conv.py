@@ -333,6 +333,99 @@ class MeanHW(torch.autograd.Function):
         return (g * (1.0 / (H * W))).view(N, 1, 1, C).expand(N, H, W, C)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Dropout on the HIP path (csrc/dropout.hip; the stream's contract is in include/delora_hip.h).  The three sites of the reference
+# (src/models/resnet_modified.py:95-118): the stacked input (inside the stem's transposing copy), the channels of layer3's output
+# (``ChannelDropout`` between two trunk segments) and the fc output (inside the fused heads).
+SITE_INPUT, SITE_CHANNELS, SITE_FC = 1, 2, 3
+_SEED_MIX = 0x9E3779B97F4A7C15
+
+
+def draw_seed(device):
+    """One 64-bit seed for the three sites of a forward pass, drawn ON THE DEVICE by torch's generator: ``torch.manual_seed`` governs
+    it, and a captured graph draws a fresh one on every replay (torch registers its generator with the capture)."""
+    return torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, device=device)
+
+
+def mix_rank(seed, rank, world_size):
+    """The seed of one rank of several: ranks seeded alike must not drop alike.  A device-side xor with a constant of the rank
+    (splitmix64's finaliser of rank + 1); a single process keeps the seed as drawn."""
+    if world_size <= 1:
+        return seed
+    z = ((int(rank) + 1) * _SEED_MIX) & (2 ** 64 - 1)
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & (2 ** 64 - 1)
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & (2 ** 64 - 1)
+    z ^= z >> 31
+    return seed ^ (z - 2 ** 64 if z >= 2 ** 63 else z)
+
+
+def dropout_scale(seed, site, p, n):
+    """``scale [n]`` fp32 = 0 or 1 / (1 - p) for the n decisions of a site (``dl_dropout_scale_f32``); seed = int64 device tensor."""
+    lib = _lib.load()
+    scale = torch.empty((int(n),), dtype=torch.float32, device=seed.device)
+    _lib.check(lib.dl_dropout_scale_f32(_ptr(seed), int(site), float(p), int(n), _ptr(scale), _stream()), "dl_dropout_scale_f32")
+    return scale
+
+
+def stem_input_drop(x, seed, p):
+    """Planar ``[N,C,H,W]`` fp32 -> channels-last ``[N,H,W,C]`` with the site-1 dropout applied on the way (one launch)."""
+    lib = _lib.load()
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    x8 = torch.empty((N, H, W, C), dtype=torch.float32, device=x.device)
+    _lib.check(lib.dl_stem_input_nhwc_drop_f32(_ptr(x), N, C, H, W, _ptr(seed), float(p), _ptr(x8), _stream()), "dl_stem_input_nhwc_drop_f32")
+    return x8
+
+
+_DTYPE_CODE_ANY = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}         # DL_DTYPE_F32 / _F16 / _BF16
+
+
+class ChannelDropout(torch.autograd.Function):
+    """``y = x * scale[n][c]`` on a channels-last map between two trunk segments (Dropout2d of the reference,
+    src/models/resnet_modified.py:112), fp32 / fp16 / bf16.  It sits at a cut of the trunk, where gradients travel in the segments'
+    private convention, and serves either arrangement:
+      * ``act = 0`` (what ``_run_segments`` uses): the segment behind it is handed the UN-dropped x as the source of its activation
+        derivative (``first`` = that tensor), so the gradient arriving here already carries ``act'(x)`` and the backward is
+        ``g * scale`` -- exact for scale 0 and 1, hence bit-identical to the uncut trunk when nothing is dropped;
+      * ``act != 0``: behind a segment run with ``first=True`` it RECEIVES a true ``dL/dy`` and RETURNS ``g * scale * act'(x)`` in one
+        pass (``dl_channel_scale_bwd_act_nhwc_t``) from the saved un-dropped x.  In half precision the true ``dL/dy`` is one more stored
+        -- rounded -- tensor than the uncut trunk has: measured 6e-3 (bf16) / 7e-4 (fp16) of conv1's weight gradient at p = 0, which
+        is why the trunk does not use this arrangement."""
+
+    @staticmethod
+    def forward(ctx, x, scale, act):
+        x = x.contiguous()
+        ctx.save_for_backward(*((x, scale) if act else (scale,)))
+        ctx.act = int(act)
+        return channel_scale(x, scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        if not ctx.act:
+            (scale,) = ctx.saved_tensors
+            g_pre = channel_scale(g, scale)
+        else:
+            lib = _lib.load()
+            x, scale = ctx.saved_tensors
+            N, H, W, C = x.shape
+            g_pre = torch.empty_like(x)
+            _lib.check(lib.dl_channel_scale_bwd_act_nhwc_t(_ptr(g), _ptr(x), _ptr(scale), N, H * W, C, ctx.act, _DTYPE_CODE_ANY[x.dtype], _ptr(g_pre),
+                                                           _stream()), "dl_channel_scale_bwd_act_nhwc_t")
+        if BACKWARD_TRACE is not None:
+            BACKWARD_TRACE.append(("channel_dropout", g.shape[3]))
+        return g_pre, None, None
+
+
+def channel_scale(x, scale):
+    """``x [N,H,W,C] * scale [N,C]`` (``dl_channel_scale_nhwc_t``; fp32 arithmetic, one rounding to x's type)."""
+    lib = _lib.load()
+    N, H, W, C = x.shape
+    y = torch.empty_like(x)
+    _lib.check(lib.dl_channel_scale_nhwc_t(_ptr(x), _ptr(scale), N, H * W, C, _DTYPE_CODE_ANY[x.dtype], _ptr(y), _stream()), "dl_channel_scale_nhwc_t")
+    return y
+
+
 def stem_supported(x_shape, out_channels):
     """Whether RingStem takes an input ``[N,C,H,W]``: 8 input channels per chunk, 64-channel output tiles, a width that halves twice."""
     N, C, H, W = x_shape
@@ -346,20 +439,32 @@ class RingStem(torch.autograd.Function):
     pooling kernel.  Backward: pooling backward + activation derivative + conv1's weight gradient in ONE kernel
     (``dl_stem_wgrad_f32``); only when the gradient with respect to the INPUT image is wanted (never in training: the range image
     is data) the three steps run separately with the library's convolution backward.  The 134 MB pre-pooling map is kept for
-    the backward (the pooled output is not: the trunk saves it)."""
+    the backward (the pooled output is not: the trunk saves it).
+
+    An optional fourth argument ``drop = (seed, p)`` applies the element-wise input dropout (site 1 of csrc/dropout.hip) inside the
+    transposing copy (``dl_stem_input_nhwc_drop_f32``); the dropped channels-last image is what the backward's weight gradient reads.
+    No mask is stored: the gradient with respect to the input image regenerates it from the saved seed."""
 
     @staticmethod
-    def forward(ctx, x, w1, act):
-        x8 = x.permute(0, 2, 3, 1).contiguous()
+    def forward(ctx, x, w1, act, *drop):
+        if drop and drop[0] is not None:
+            seed, p = drop[0]
+            x8 = stem_input_drop(x, seed, p)
+            ctx.drop_p = float(p)
+        else:
+            seed = None
+            x8 = x.permute(0, 2, 3, 1).contiguous()
+        ctx.n_extra = len(drop)
         a = conv_nhwc(x8, weight_storage(w1), stride=(1, 2), act=act, epilogue=EPI_ACT if act else 0)
         y, win = pool_fwd(a)
-        ctx.save_for_backward(x8, a, win, w1)
+        ctx.save_for_backward(x8, a, win, w1, *([seed] if seed is not None else []))
         ctx.act = act
         return y
 
     @staticmethod
     def backward(ctx, g):
-        x8, a, win, w1 = ctx.saved_tensors
+        x8, a, win, w1, *seed = ctx.saved_tensors
+        extra = (None,) * ctx.n_extra
         want_x = ctx.needs_input_grad[0]
         lib = _lib.load()
         N, H, W, _ = x8.shape
@@ -371,7 +476,7 @@ class RingStem(torch.autograd.Function):
             dw = torch.empty((64, 8, 3, 3), dtype=torch.float32, device=x8.device)
             _lib.check(lib.dl_stem_wgrad_f32(_ptr(g.contiguous()), _ptr(a), _ptr(win), _ptr(x8), N, H, W, int(ctx.act), _ptr(ws), _ptr(dw),
                                              _stream()), "dl_stem_wgrad_f32")
-            return None, dw, None
+            return (None, dw, None) + extra
         gc = pool_bwd(g.contiguous(), a, win, ctx.act)
         xp = torch.cat((x8[:, :, -1:], x8, x8[:, :, :1]), dim=2).permute(0, 3, 1, 2)       # wrapped, channels_last strides
         gx, dw, _ = torch.ops.aten.convolution_backward(gc.permute(0, 3, 1, 2), xp, w1, None, (1, 2), (1, 0), (1, 1), False,
@@ -381,7 +486,9 @@ class RingStem(torch.autograd.Function):
             gx = gxp[..., 1:-1].clone()
             gx[..., -1] += gxp[..., 0]
             gx[..., 0] += gxp[..., -1]
-        return (gx if want_x else None), dw, None
+            if seed:                                   # the input went through the dropout: the same mask, from the saved seed
+                gx = gx * dropout_scale(seed[0], SITE_INPUT, ctx.drop_p, x8.numel()).view(x8.shape).permute(0, 3, 1, 2)
+        return ((gx if want_x else None), dw, None) + extra
 
 
 # How the trunk is cut into autograd Functions.  Each Function hands its weight gradients to autograd when its backward has run, so
@@ -458,7 +565,9 @@ class RingSegment(torch.autograd.Function):
     the consumer folds that factor into the epilogue of its input-gradient convolution (``EPI_DACT``): no elementwise kernel
     runs between two convolutions, across segment boundaries either.  Only the ``last`` segment receives a true ``dL/dy`` (from
     the pooling) and applies ``act'`` itself; only the ``first`` one returns a true ``dL/dx`` (x = the pooled stem output,
-    whose activation derivative belongs to the stem)."""
+    whose activation derivative belongs to the stem).  ``first`` may also be a TENSOR: the activated map x0 was derived from by a
+    per-channel scaling (``ChannelDropout``) -- the returned gradient is then multiplied by ``act'`` of THAT map in the same epilogue
+    (``act'`` of a dropped map would be ``1 - (1.25 y)^2``), and the scaling's own backward is a plain multiplication."""
 
     @staticmethod
     def forward(ctx, x0, act, blocks, first, last, *weights):
@@ -503,11 +612,13 @@ class RingSegment(torch.autograd.Function):
             ubwd += [ub1, ub2]
             saved += [y1, y2]
             x = y2
-        ctx.act, ctx.blocks, ctx.first, ctx.last = act, blocks, first, last
+        dsrc0 = first if torch.is_tensor(first) else None
+        ctx.act, ctx.blocks, ctx.first, ctx.last = act, blocks, dsrc0 is None and bool(first), last
         # the Winograd-domain backward weights travel with the saved tensors (released with the graph, covered by autograd's
         # in-place version check like the raw weights); layers on the direct kernel have none
         ctx.ubwd_mask = tuple(u is not None for u in ubwd)
-        ctx.save_for_backward(*saved, *weights, *[u for u in ubwd if u is not None])
+        ctx.has_dsrc0 = dsrc0 is not None
+        ctx.save_for_backward(*saved, *weights, *[u for u in ubwd if u is not None], *([dsrc0] if dsrc0 is not None else []))
         return x
 
     @staticmethod
@@ -515,6 +626,9 @@ class RingSegment(torch.autograd.Function):
         act, blocks = ctx.act, ctx.blocks
         nb = len(blocks)
         saved = ctx.saved_tensors
+        dsrc0 = None
+        if ctx.has_dsrc0:
+            saved, dsrc0 = saved[:-1], saved[-1]
         nu = sum(ctx.ubwd_mask)
         acts, weights = saved[:1 + 2 * nb], saved[1 + 2 * nb:len(saved) - nu]
         u_it = iter(saved[len(saved) - nu:])
@@ -537,6 +651,7 @@ class RingSegment(torch.autograd.Function):
             w1p, w2p = weights[wi], weights[wi + 1]
             x, y1 = acts[2 * b], acts[2 * b + 1]
             first = ctx.first and b == 0                    # x0 is the pooled stem output: its act' belongs to the stem
+            xd = dsrc0 if (b == 0 and dsrc0 is not None) else x      # the map whose act' the returned gradient carries
             pending.append((wi + 1, (y1, g2, 3, (1, 1))))
             ub1, ub2 = ubwd[2 * b], ubwd[2 * b + 1]
             if ub2 is not None:
@@ -547,37 +662,51 @@ class RingSegment(torch.autograd.Function):
             if not has_ds:
                 epi = EPI_ADD if first else (EPI_ADD | EPI_DACT)
                 if ub1 is not None:
-                    g2 = wino_conv(g1, ub1, cin, act=act, epilogue=epi, add=g2, dsrc=None if first else x)
+                    g2 = wino_conv(g1, ub1, cin, act=act, epilogue=epi, add=g2, dsrc=None if first else xd)
                 else:
-                    g2 = conv_nhwc(g1, weight_storage(w1p), act=act, epilogue=epi, add=g2, dsrc=None if first else x, transposed=True)
+                    g2 = conv_nhwc(g1, weight_storage(w1p), act=act, epilogue=epi, add=g2, dsrc=None if first else xd, transposed=True)
             else:
                 wdp = weights[wi + 2]
                 pending.append((wi + 2, (x, g2, 1, stride)))
                 # down-sampling branch on the grid, then one pass per stride phase of the 3x3 layer with it and act'(x) fused
                 dxb = dgrad_strided(g2, weight_storage(wdp), stride, x.shape[1:3], dense=True)
                 epi = EPI_ADD_GRID if first else (EPI_ADD_GRID | EPI_DACT)
-                g2 = dgrad_strided(g1, weight_storage(w1p), stride, x.shape[1:3], act=act, epilogue=epi, add_grid=dxb, dsrc=None if first else x)
+                g2 = dgrad_strided(g1, weight_storage(w1p), stride, x.shape[1:3], act=act, epilogue=epi, add_grid=dxb, dsrc=None if first else xd)
         pending.flush()
         if BACKWARD_TRACE is not None:
             BACKWARD_TRACE.append(("segment", blocks[0][0], blocks[-1][1], nb))
         return (g2, None, None, None, None, *grads)
 
 
-def _run_segments(fn, x, act, blocks, weights, mode, last_applies_act):
+def _run_segments(fn, x, act, blocks, weights, mode, last_applies_act, channel_drop=None):
+    """``channel_drop = (scale [N][C], b)``: ``ChannelDropout`` in front of block b -- an extra cut there in every mode.  The segment
+    behind it takes the UN-dropped map as the source of the activation derivative of the gradient it returns (``first`` = that
+    tensor), the dropout's backward multiplies by the scale, and the segment in front of it stays at ``last=False``: it receives a
+    pre-activation gradient exactly as without the cut."""
     segs = _segments(blocks, mode or TRUNK_SEGMENTS)
+    cut = None
+    if channel_drop is not None:
+        scale, cut = channel_drop
+        if not 0 < cut < len(blocks):
+            raise ValueError(f"channel dropout in front of block {cut} of {len(blocks)}")
+        segs = [part for (b0, b1) in segs for part in (((b0, cut), (cut, b1)) if b0 < cut < b1 else ((b0, b1),))]
     wi = 0
     for i, (b0, b1) in enumerate(segs):
         nw = sum(3 if blocks[b][3] else 2 for b in range(b0, b1))
-        x = fn.apply(x, act, tuple(blocks[b0:b1]), i == 0, last_applies_act and i == len(segs) - 1, *weights[wi:wi + nw])
+        first = i == 0
+        if b0 == cut:
+            first, x = x, ChannelDropout.apply(x, scale, 0)
+        x = fn.apply(x, act, tuple(blocks[b0:b1]), first, last_applies_act and i == len(segs) - 1, *weights[wi:wi + nw])
         wi += nw
     return x
 
 
-def ring_trunk(x0, act, blocks, weights, segments=None):
+def ring_trunk(x0, act, blocks, weights, segments=None, channel_drop=None):
     """layer1..layer4 of the pose CNN: x0 ``[N,H,W,C0]`` channels-last fp32, already activated (the pooled stem output); blocks =
     tuple of (cin, cout, stride, has_downsample); weights in block order (conv1, conv2[, downsample]).  Returns the last
-    feature map ``[N,H',W',C']``.  ``segments``: how the trunk is cut into autograd Functions (default ``TRUNK_SEGMENTS``)."""
-    return _run_segments(RingSegment, x0, act, blocks, list(weights), segments, True)
+    feature map ``[N,H',W',C']``.  ``segments``: how the trunk is cut into autograd Functions (default ``TRUNK_SEGMENTS``).
+    ``channel_drop``: (scale ``[N][C]``, block index) -- channel dropout on the input of that block (see ``_run_segments``)."""
+    return _run_segments(RingSegment, x0, act, blocks, list(weights), segments, True, channel_drop)
 
 
 class RingTrunk:
@@ -724,10 +853,12 @@ class RingSegmentH(torch.autograd.Function):
             wbs += [w1b, w2b] + ([wdb] if has_ds else [])
             saved += [y1, y2]
             x = y2
-        ctx.act, ctx.blocks, ctx.first, ctx.last = act, blocks, first, last
+        dsrc0 = first if torch.is_tensor(first) else None           # see RingSegment
+        ctx.act, ctx.blocks, ctx.first, ctx.last = act, blocks, dsrc0 is None and bool(first), last
         ctx.n_w = len(weights)
         ctx.w_meta = [(tuple(w.shape), tuple(w.stride())) for w in weights]
-        ctx.save_for_backward(*saved, *(wbs if need_bwd else []))
+        ctx.has_dsrc0 = dsrc0 is not None
+        ctx.save_for_backward(*saved, *(wbs if need_bwd else []), *([dsrc0] if dsrc0 is not None else []))
         return x
 
     @staticmethod
@@ -735,6 +866,9 @@ class RingSegmentH(torch.autograd.Function):
         act, blocks = ctx.act, ctx.blocks
         nb = len(blocks)
         saved = ctx.saved_tensors
+        dsrc0 = None
+        if ctx.has_dsrc0:
+            saved, dsrc0 = saved[:-1], saved[-1]
         acts, wbs = saved[:1 + 2 * nb], saved[1 + 2 * nb:]
         grads = [None] * ctx.n_w
         g2 = dy.contiguous()
@@ -754,17 +888,18 @@ class RingSegmentH(torch.autograd.Function):
             w1b, w2b = wbs[wi], wbs[wi + 1]
             x, y1 = acts[2 * b], acts[2 * b + 1]
             first = ctx.first and b == 0
+            xd = dsrc0 if (b == 0 and dsrc0 is not None) else x
             pending.append((wi + 1, (y1, g2, 3, (1, 1))))
             g1 = conv_nhwc_h(g2, w2b, 3, act=act, epilogue=EPI_DACT, dsrc=y1, transposed=True)
             pending.append((wi, (x, g1, 3, stride)))
             if not has_ds:
                 epi = EPI_ADD if first else (EPI_ADD | EPI_DACT)
-                g2 = conv_nhwc_h(g1, w1b, 3, act=act, epilogue=epi, add=g2, dsrc=None if first else x, transposed=True)
+                g2 = conv_nhwc_h(g1, w1b, 3, act=act, epilogue=epi, add=g2, dsrc=None if first else xd, transposed=True)
             else:
                 pending.append((wi + 2, (x, g2, 1, stride)))
                 dxb = dgrad_strided_h(g2, wbs[wi + 2], 1, stride, x.shape[1:3], dense=True)
                 epi = EPI_ADD_GRID if first else (EPI_ADD_GRID | EPI_DACT)
-                g2 = dgrad_strided_h(g1, w1b, 3, stride, x.shape[1:3], act=act, epilogue=epi, add_grid=dxb, dsrc=None if first else x)
+                g2 = dgrad_strided_h(g1, w1b, 3, stride, x.shape[1:3], act=act, epilogue=epi, add_grid=dxb, dsrc=None if first else xd)
         pending.flush()
         if BACKWARD_TRACE is not None:
             BACKWARD_TRACE.append(("segment", blocks[0][0], blocks[-1][1], nb))
@@ -797,10 +932,10 @@ class MeanHWActH(torch.autograd.Function):
         return g, None
 
 
-def ring_trunk_h(x0, act, blocks, dtype, weights, segments=None):
+def ring_trunk_h(x0, act, blocks, dtype, weights, segments=None, channel_drop=None):
     """layer1..layer4 + global average pooling in half precision: x0 ``[N,H,W,C0]`` fp32 channels-last (the pooled stem output),
     fp32 parameters in block order; returns the pooled features ``[N,C']`` in fp32."""
-    x = _run_segments(RingSegmentH, CastToHalf.apply(x0, dtype), act, blocks, list(weights), segments, False)
+    x = _run_segments(RingSegmentH, CastToHalf.apply(x0, dtype), act, blocks, list(weights), segments, False, channel_drop)
     return MeanHWActH.apply(x, act)
 
 

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DL_ABI_VERSION 7   /* 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
+#define DL_ABI_VERSION 8   /* 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
 
 typedef void* dl_stream;
 
@@ -466,6 +466,46 @@ size_t dl_heads_bwd_workspace_bytes(int32_t B, int32_t F, int32_t R, int32_t Hd)
 int dl_heads_bwd(const float* x, const dl_heads_params* params, int32_t B, int32_t F, int32_t R, int32_t Hd, int32_t act, const float* a1,
                  const float* a2, const float* rot_raw, const float* norm, const float* grad_translation, const float* grad_rotation,
                  const dl_heads_params* grads, float* grad_x, void* workspace, dl_stream stream);
+
+/* The same two calls with dropout on the fc output (reference src/models/resnet_modified.py:118: `dropout_values(fc(x))`): fc_scale
+ * [B][R] holds 0 or 1 / (1 - p) per element (dl_dropout_scale_f32, site 3), or is NULL.  Forward: a1 = act((fc(x) + bias) * fc_scale);
+ * backward: the gradient with respect to the fc output additionally times fc_scale.  With fc_scale == NULL they ARE dl_heads_fwd /
+ * dl_heads_bwd (one implementation). */
+int dl_heads_fwd_drop(const float* x, const dl_heads_params* params, int32_t B, int32_t F, int32_t R, int32_t Hd, int32_t act,
+                      const float* fc_scale, float* a1, float* a2, float* rot_raw, float* translation, float* rotation, float* norm,
+                      dl_stream stream);
+int dl_heads_bwd_drop(const float* x, const dl_heads_params* params, int32_t B, int32_t F, int32_t R, int32_t Hd, int32_t act,
+                      const float* fc_scale, const float* a1, const float* a2, const float* rot_raw, const float* norm,
+                      const float* grad_translation, const float* grad_rotation, const dl_heads_params* grads, float* grad_x,
+                      void* workspace, dl_stream stream);
+
+/*
+ * Dropout of the pose CNN (csrc/dropout.hip; reference src/models/resnet_modified.py:33-38, :95-118: p = 0.2, training mode only).
+ * The random stream is this library's own and has a contract a host program can replay:
+ *   generator   Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85)
+ *   counter     (i >> 2, i >> 34, site, 0) for decision index i; key = (seed & 0xffffffff, seed >> 32); decision i reads word i & 3
+ *   site        1 = the stacked input image, 2 = the channels of layer3's output, 3 = the fc output
+ *   decision    dropped iff word < round(p * 2^32) (p = 0.2: 0x33333333), else multiplied by 1.0f / (1.0f - (float)p);
+ *               p = 0 keeps everything with a scale of exactly 1.0f.  0 <= p < 1.
+ *   index i     the flat index of the element in the tensor the kernel writes: [N][H][W][C] channels-last for the input (a pixel's C
+ *               channels are C / 4 generator calls), n * C + c for the channels, b * R + j for fc.  It does not depend on the storage type.
+ *   seed        ONE 64-bit value read FROM DEVICE MEMORY by the kernel (a replayed graph sees the value its replay wrote).
+ *
+ *   dl_dropout_scale_f32         scale[i] = 0 or 1 / (1 - p) for the n decisions of a site (the two small masks; any site's, for tests)
+ *   dl_stem_input_nhwc_drop_f32  x_nchw [N][C][H][W] planar -> x_nhwc [N][H][W][C] times the site-1 mask: the transposing copy in front
+ *                                of the stem's convolution with the dropout applied on the way (no extra pass, no stored mask).  C % 4 == 0.
+ *   dl_channel_scale_nhwc_t      y[n][p][c] = x[n][p][c] * scale[n][c] on a channels-last map [N][P][C] (P = H * W pixels) of dtype
+ *                                DL_DTYPE_F32 / _F16 / _BF16; fp32 arithmetic, one rounding.  C % 4 == 0 (fp32) / C % 8 == 0 (half).
+ *   dl_channel_scale_bwd_act_nhwc_t   g_pre[n][p][c] = g[n][p][c] * scale[n][c] * act'(x[n][p][c]) in ONE pass, x = the activated,
+ *                                UN-dropped map (act 0 none, 1 tanh: 1 - x^2, 2 relu: x > 0): the gradient with respect to the
+ *                                pre-activation of the layer that produced x, as the trunk's segments exchange it.
+ */
+int dl_dropout_scale_f32(const uint64_t* seed, uint32_t site, double p, int64_t n, float* scale, dl_stream stream);
+int dl_stem_input_nhwc_drop_f32(const float* x_nchw, int32_t N, int32_t C, int32_t H, int32_t W, const uint64_t* seed, double p,
+                                float* x_nhwc, dl_stream stream);
+int dl_channel_scale_nhwc_t(const void* x, const float* scale, int32_t N, int32_t P, int32_t C, int32_t dtype, void* y, dl_stream stream);
+int dl_channel_scale_bwd_act_nhwc_t(const void* g, const void* x, const float* scale, int32_t N, int32_t P, int32_t C, int32_t act,
+                                    int32_t dtype, void* g_pre, dl_stream stream);
 
 /* Quaternion (x,y,z,w) + translation -> T [B][4][4] = [[R, t], [0, 1]] and its backward (reference src/models/model_parts.py:
  * 24-44; R = kornia 0.3.0 quaternion_to_rotation_matrix: normalise with eps, then the element-wise formula):
