@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdelora_hip.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class DeloraHipError(RuntimeError):
@@ -49,6 +49,10 @@ SIGNATURES = {
     "dl_icp_loss_partial_timed": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _u32, _vp, _vp, _vp]),
     "dl_probe_stream_read": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp]),
     "dl_nn_bruteforce": (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp]),
+    "dl_nn_list_tree_bytes": (_sz, [_i32]),
+    "dl_nn_list_query_workspace_bytes": (_sz, [_i32]),
+    "dl_nn_list_build": (_i32, [_vp, _i64, _i32, _vp, _vp]),
+    "dl_nn_list_query": (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "dl_ring_act_pad_fwd": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
     "dl_ring_act_pad_bwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dl_ring_act_pad_fwd_t": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),

@@ -288,6 +288,56 @@ def nn_bruteforce(src, tgt):
     return nn
 
 
+def _list(t):
+    """Dense fp32 ``[3,M]`` view of a point list (a view into a larger tensor keeps its column stride)."""
+    t = t.detach()
+    if t.dim() != 2 or t.shape[0] != 3:
+        raise ValueError(f"expected a [3,M] point list, got {tuple(t.shape)}")
+    if t.dtype != torch.float32 or (t.shape[1] > 0 and (t.stride(1) != 1 or t.stride(0) < t.shape[1])):
+        t = t.contiguous().float()
+    return t, (t.stride(0) if t.shape[1] > 0 else 1)
+
+
+class PointTree:
+    """Exact nearest-neighbour tree over a free-form target list ``tgt [3,Mt]`` (dl_nn_list_build): what the reference builds
+    with ``scipy.spatial.cKDTree``.  ``query(src [3,Ms])`` returns the int32 index of the nearest target for every column, the
+    same index ``nn_bruteforce`` returns (lowest index among exact ties, -1 where there is no finite answer).  The tree owns its
+    buffer and a reference to the target tensor; build and queries run on the current stream."""
+
+    def __init__(self, tgt):
+        lib = _lib.load()
+        _require_cuda(tgt)
+        self.tgt, self._cs = _list(tgt)
+        self.Mt = int(self.tgt.shape[1])
+        self.device = self.tgt.device
+        self._tree = torch.empty((lib.dl_nn_list_tree_bytes(self.Mt),), dtype=torch.uint8, device=self.device)
+        self._ws = None
+        self.rebuild()
+
+    def rebuild(self):
+        """Build again from the current contents of the target tensor, into the same buffer (a target list refreshed in place,
+        e.g. between replays of a captured graph)."""
+        _lib.check(_lib.load().dl_nn_list_build(_ptr(self.tgt), self._cs, self.Mt, _ptr(self._tree), _stream()), "dl_nn_list_build")
+        return self
+
+    def query(self, src, out=None):
+        lib = _lib.load()
+        _require_cuda(src)
+        src, cs = _list(src)
+        if src.device != self.device:
+            raise ValueError(f"PointTree on {self.device} queried with points on {src.device}")
+        Ms = int(src.shape[1])
+        nn = out if out is not None else torch.empty((Ms,), dtype=torch.int32, device=self.device)
+        if nn.dtype != torch.int32 or nn.shape != (Ms,) or not nn.is_contiguous() or nn.device != self.device:
+            raise ValueError("out must be a contiguous int32 [Ms] tensor on the tree's device")
+        need = lib.dl_nn_list_query_workspace_bytes(Ms)
+        if self._ws is None or self._ws.numel() < need:          # kept between queries (stream-ordered reuse, as torch's own allocator)
+            self._ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.device)
+        _lib.check(lib.dl_nn_list_query(_ptr(src), cs, Ms, _ptr(self.tgt), self._cs, self.Mt, _ptr(self._tree), _ptr(nn),
+                                        _ptr(self._ws), _stream()), "dl_nn_list_query")
+        return nn
+
+
 def probe_stream_read(src_image4, src_normals, match, nn_pix):
     """Launch the read-only twin of the loss kernel on the same operands (measurement aid, see dl_probe_stream_read)."""
     lib = _lib.load()

@@ -2,8 +2,9 @@
 
 The training step does not go through this class (it uses the fused image-based kernels of
 delora_amd.geometry); it exists so that code written against the reference's list interface keeps working:
-correspondences come from the exhaustive HIP nearest-neighbour kernel, the loss arithmetic on the gathered
-pairs is a handful of torch ops so that gradients flow into the (already transformed) inputs as they do in
+correspondences come from the exact HIP tree search over the target list (``geometry.PointTree``, the counterpart of the
+reference's cKDTree; small lists stay on the quadratic kernel, which returns the same indices), the loss arithmetic on the
+gathered pairs is a handful of torch ops so that gradients flow into the (already transformed) inputs as they do in
 the reference."""
 import torch
 
@@ -18,13 +19,27 @@ class ICPLosses(torch.nn.Module):
             raise Exception("The normal loss which is defined here is not admissible.")
 
     _warned_quadratic = False
+    # Source points x target points from which a search goes through the tree.  Read off profiles/nn_list_bench.json (one MI355X,
+    # Ms = Mt = n, build + query against the exhaustive kernel, ms per call over the four pose regimes): n = 8 192: 0.40-0.53
+    # against 0.33, the exhaustive kernel still wins; n = 32 768: 0.44-0.71 against 1.34, the tree wins in every regime
+    # (131 072: 0.72-1.37 against 8.0).  The crossover is the smallest measured size at which the tree wins everywhere.
+    tree_min_pairs = 32768 * 32768
 
     @staticmethod
-    def find_target_correspondences(target_point_cloud, source_point_cloud):
-        """Index of the exact nearest target point for every source point (both ``[1,3,M]``).  The list interface has no image lattice to
-        search on, so this is the exhaustive O(M^2) kernel: 17 G distance evaluations per call for two 64x2048 scans.  Said once, loudly,
-        above 32 k points -- the training step (``Deployer.step``) uses the lattice search of ``geometry.nn_correspond`` instead."""
+    def _wants_tree(n_src, n_tgt):
+        return n_src * n_tgt >= ICPLosses.tree_min_pairs
+
+    @staticmethod
+    def find_target_correspondences(target_point_cloud, source_point_cloud, tree=None):
+        """Index of the exact nearest target point for every source point (both ``[1,3,M]``): tree search (``geometry.PointTree``,
+        built here unless the caller passes the one it already holds for this target list), or the exhaustive kernel for lists too
+        small for the tree to pay.  Both give the same indices.  Only a call that really goes the quadratic way above 32 k points
+        says so, once."""
         n_src, n_tgt = int(source_point_cloud.shape[-1]), int(target_point_cloud.shape[-1])
+        if tree is None and ICPLosses._wants_tree(n_src, n_tgt):
+            tree = geometry.PointTree(target_point_cloud[0])
+        if tree is not None:
+            return tree.query(source_point_cloud[0]).long()
         if max(n_src, n_tgt) > 32768 and not ICPLosses._warned_quadratic:
             ICPLosses._warned_quadratic = True
             import warnings
@@ -42,7 +57,7 @@ class ICPLosses(torch.nn.Module):
         if cfg["po2po_alone"]:                                             # icp_losses.py:36-45
             if cfg["point_to_plane_loss"] or cfg["plane_to_plane_loss"]:       # the reference dies here (:135-146)
                 raise Exception("po2po_alone needs point_to_plane_loss and plane_to_plane_loss switched off.")
-            nn = self.find_target_correspondences(target_point_cloud, source_point_cloud_transformed)
+            nn = self.find_target_correspondences(target_point_cloud, source_point_cloud_transformed)     # builds its own tree
             if cfg["point_to_point_loss"]:
                 d = source_point_cloud_transformed - target_point_cloud[:, :, nn]
                 losses["loss_po2po"] = (d * d).mean()
@@ -51,10 +66,14 @@ class ICPLosses(torch.nn.Module):
         t_has = (target_normal_list[0] != 0).any(dim=0)                      # :51-52
         src_w = source_point_cloud_transformed[:, :, s_has]
         srcn_w = source_normal_list_transformed[:, :, s_has]
-        nn_w = self.find_target_correspondences(target_point_cloud, src_w)
+        # ONE tree per call, shared by both searches (decided on the whole source list: the two searches split it between them)
+        n_tgt = int(target_point_cloud.shape[-1])
+        tree = (geometry.PointTree(target_point_cloud[0])
+                if self._wants_tree(int(source_point_cloud_transformed.shape[-1]), n_tgt) else None)
+        nn_w = self.find_target_correspondences(target_point_cloud, src_w, tree)
         if cfg["point_to_point_loss"]:                                     # :85-100: neither side has a normal
             src_wo = source_point_cloud_transformed[:, :, ~s_has]
-            nn_wo = self.find_target_correspondences(target_point_cloud, src_wo)
+            nn_wo = self.find_target_correspondences(target_point_cloud, src_wo, tree)
             keep = ~t_has[nn_wo]
             d = src_wo[:, :, keep] - target_point_cloud[:, :, nn_wo[keep]]
             losses["loss_po2po"] = (d * d).mean()

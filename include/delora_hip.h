@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DL_ABI_VERSION 8   /* 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
+#define DL_ABI_VERSION 9   /* 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
 
 typedef void* dl_stream;
 
@@ -198,6 +198,32 @@ int dl_icp_loss_bwd(const float* grad_terms, const float* grad_loss_terms, int32
  */
 int dl_nn_bruteforce(const float* src, int64_t ms_cs, int32_t Ms, const float* tgt, int64_t mt_cs,
                      int32_t Mt, int32_t* nn, dl_stream stream);
+
+/*
+ * The same search through a tree: exact nearest neighbour between two free-form point lists in O(M log M), what the
+ * reference does with scipy.spatial.cKDTree (src/losses/icp_losses.py:24-34: one tree over the target list, one query per
+ * source list; called once per sample from src/deploy/deployer.py:302-307).  Built once per target list, queried any
+ * number of times.  The answer is dl_nn_bruteforce's on every input: the target that minimises dx*dx + dy*dy + dz*dz in fp64
+ * on the fp32 coordinates, the LOWEST target index among exact ties, -1 for a query with a non-finite coordinate or when no
+ * target is finite (Mt == 0 included); a target with a non-finite coordinate is never returned.  Bitwise reproducible.
+ *   tgt [3][mt_cs], src [3][ms_cs] planar fp32 (column strides >= the counts); nn [Ms] out, index into tgt in the caller's order
+ *   Ms, Mt free, 0 included, at most 2^30 (DL_ERR_UNSUPPORTED beyond: indices are 32-bit)
+ *   tree       caller-owned, 16-byte aligned, dl_nn_list_tree_bytes(Mt) bytes:
+ *                8192 + 40 * P + 32 * nodes + 1024 * ceil(Mt / 2048),  P = Mt rounded up to a multiple of 64 (the leaf size),
+ *                nodes = P/64 leaves + ceil(leaves/64) + ... down to the first level of at most 64 nodes
+ *              (per point: 16 B packed record + 2 x 8 B sort keys + 2 x 4 B sort indices, ~0.5 B of boxes, 0.5 B of digit counts)
+ *              It holds its own copy of the coordinates: the target list may change after the build without affecting queries.
+ *   workspace  caller-owned, 16-byte aligned, dl_nn_list_query_workspace_bytes(Ms) bytes:
+ *                24 * Q + 1024 * ceil(Ms / 2048),  Q = Ms rounded up to a multiple of 64.  One query at a time per workspace.
+ *   The size functions return 0 for a negative count or one above 2^30.  tgt / mt_cs of the query are accepted for symmetry
+ *   with dl_nn_bruteforce and may be NULL / 0 (the tree is self-contained); Mt must be the count the tree was built with.
+ * Neither call synchronises, allocates or reads back: both can be captured into a HIP graph (a linear chain of kernels).
+ */
+size_t dl_nn_list_tree_bytes(int32_t Mt);
+size_t dl_nn_list_query_workspace_bytes(int32_t Ms);
+int dl_nn_list_build(const float* tgt, int64_t mt_cs, int32_t Mt, void* tree, dl_stream stream);
+int dl_nn_list_query(const float* src, int64_t ms_cs, int32_t Ms, const float* tgt, int64_t mt_cs, int32_t Mt,
+                     const void* tree, int32_t* nn, void* workspace, dl_stream stream);
 
 /*
  * Fused elementwise glue of the pose CNN: out[r][pad + w] = act(x[r][w] + res[r][w]) plus, for pad == 1, the two
