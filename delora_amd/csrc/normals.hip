@@ -18,7 +18,9 @@
 //  * partial sums of at most 11 terms per accumulator, combined in fp64; covariance about the mean in fp64;
 //  * eigenvector of the smallest eigenvalue: closed-form eigenvalue in fp32 as a starting shift, then
 //    division-free Rayleigh-quotient iteration in fp64 (x <- adj(A - mu I) x, cubic convergence), no
-//    data-dependent loop.  The result is the eigenvector of the fp32-moment matrix to fp64 accuracy; what
+//    data-dependent loop; where the two smallest eigenvalues nearly coincide the iteration finds a first
+//    eigenvector (the best separated one) and the normal comes from the 2x2 problem in the plane
+//    perpendicular to it.  The result is the eigenvector of the fp32-moment matrix to fp64 accuracy; what
 //    remains in a comparison with the reference is fp32 rounding of the moments on both sides.
 #include "common.h"
 
@@ -53,29 +55,24 @@ __device__ __forceinline__ void smallest_eigenvector(double a00, double a01, dou
   const float b00 = (float)a00 - third, b11 = (float)a11 - third, b22 = (float)a22 - third;
   const float f01 = (float)a01, f02 = (float)a02, f12 = (float)a12;
   const float p2 = b00 * b00 + b11 * b11 + b22 * b22 + 2.0f * (f01 * f01 + f02 * f02 + f12 * f12);
-  float lam = third;
+  // closed form in units of the trace, with s = sqrt(p2 / 6) and t = acos(r) / 3: lam_min = 1/3 + 2 s cos(t + 2 pi / 3),
+  // lam_max = 1/3 + 2 s cos(t), lam_mid - lam_min = 2 sqrt(3) s sin(t), lam_max - lam_mid = 2 sqrt(3) s sin(pi / 3 - t)
+  float lam = third, lam_top = third, gap_rel = 0.f, gap_top = 0.f;
   if (p2 > 1e-13f) {
     const float ip = __frsqrt_rn(p2 * (1.0f / 6.0f));
     const float c00 = b00 * ip, c11 = b11 * ip, c22 = b22 * ip, c01 = f01 * ip, c02 = f02 * ip, c12 = f12 * ip;
     float r = 0.5f * (c00 * (c11 * c22 - c12 * c12) - c01 * (c01 * c22 - c12 * c02) + c02 * (c01 * c12 - c11 * c02));
     r = fminf(fmaxf(r, -1.0f), 1.0f);
-    lam = third + 2.0f * (p2 * (1.0f / 6.0f) * ip) * __cosf(acosf(r) * third + 2.0943951f);
+    const float s2 = 2.0f * (p2 * (1.0f / 6.0f) * ip), t = acosf(r) * third;
+    lam = third + s2 * __cosf(t + 2.0943951f);
+    lam_top = third + s2 * __cosf(t);
+    gap_rel = s2 * 1.7320508f * __sinf(t);
+    gap_top = s2 * 1.7320508f * __sinf(1.0471976f - t);
   }
   // Round 6: where the two smallest eigenvalues are well separated -- a plane with structure in both directions, an edge: everything
   // but thin lines of points -- the eigenvector comes from the SAME construction in fp32 (adjugate column of A - lam I, one
   // Rayleigh-quotient step): its error is ~eps32 / gap <= 1e-4 at the threshold, inside the 2e-4 + 50 eps32 / gap the parity tests
   // allow, and the fp64 solve below (40 % of the kernel's instructions, at half rate) runs only in waves that hold a degenerate pixel.
-  // gap = lam_mid - lam_min = 2 sqrt(p2 / 6) sqrt(3) sin(acos(r) / 3) in units of the trace.
-  float gap_rel = 0.f;
-  {
-    if (p2 > 1e-13f) {
-      const float ip = __frsqrt_rn(p2 * (1.0f / 6.0f));
-      const float c00 = b00 * ip, c11 = b11 * ip, c22 = b22 * ip, c01 = f01 * ip, c02 = f02 * ip, c12 = f12 * ip;
-      float r = 0.5f * (c00 * (c11 * c22 - c12 * c12) - c01 * (c01 * c22 - c12 * c02) + c02 * (c01 * c12 - c11 * c02));
-      r = fminf(fmaxf(r, -1.0f), 1.0f);
-      gap_rel = 2.0f * (p2 * (1.0f / 6.0f) * ip) * 1.7320508f * __sinf(acosf(r) * third);
-    }
-  }
   if (gap_rel >= NRM_FP32_GAP) {
     const float g00 = (float)a00, g11 = (float)a11, g22 = (float)a22;
     const float m00 = g00 - lam, m11 = g11 - lam, m22 = g22 - lam;
@@ -103,7 +100,16 @@ __device__ __forceinline__ void smallest_eigenvector(double a00, double a01, dou
     nx = (double)(y0 * fix); ny = (double)(y1 * fix); nz = (double)(y2 * fix);
     return;
   }
-  const double mu = (double)lam;
+  // Below the threshold the two smallest eigenvalues are close -- a thin line of points -- and the fp32 shift cannot tell them
+  // apart: acos(r) near r = 1 turns a rounding of r (1e-7) into an error of the size of a gap of 3e-4, and a Rayleigh iteration
+  // started there converges, accurately, to the eigenvector of the MIDDLE eigenvalue on some pixels (a tangent of the line for
+  // a normal; on an exactly collinear window even to the line direction itself).  So the iteration goes for the eigenvector of
+  // whichever end of the spectrum is better separated -- the largest eigenvalue, unless all three nearly coincide -- and what it
+  // finds is only a first eigenvector x: A restricted to the plane perpendicular to x is a 2x2 problem, solved in closed form
+  // to fp64 accuracy however close its eigenvalues are, and the normal is x or that problem's smaller eigenvector, whichever has
+  // the smaller Rayleigh quotient.  Any eigenvector the iteration converges to therefore leads to the smallest one.
+  const bool from_top = gap_top > gap_rel;
+  const double mu = from_top ? (double)lam_top : (double)lam;
   double x0, x1, x2;
   {
     const double m00 = a00 - mu, m11 = a11 - mu, m22 = a22 - mu;
@@ -152,6 +158,35 @@ __device__ __forceinline__ void smallest_eigenvector(double a00, double a01, dou
   nrm = nrm * (1.5 - 0.5 * xx * nrm * nrm);
   nrm = nrm * (1.5 - 0.5 * xx * nrm * nrm);
   nx = x0 * nrm; ny = x1 * nrm; nz = x2 * nrm;
+  {
+    // orthonormal basis (u, w) of the plane perpendicular to x: u = x cross the axis x is least aligned with
+    const double f0 = fabs(nx), f1 = fabs(ny), f2 = fabs(nz);
+    double u0, u1, u2;
+    if (f0 <= f1 && f0 <= f2) { u0 = 0.0; u1 = nz; u2 = -ny; }
+    else if (f1 <= f2)        { u0 = -nz; u1 = 0.0; u2 = nx; }
+    else                      { u0 = ny; u1 = -nx; u2 = 0.0; }
+    const double un = 1.0 / sqrt(u0 * u0 + u1 * u1 + u2 * u2);   // the squared length is >= 2/3
+    u0 *= un; u1 *= un; u2 *= un;
+    const double w0 = ny * u2 - nz * u1, w1 = nz * u0 - nx * u2, w2 = nx * u1 - ny * u0;
+    const double ax0 = a00 * nx + a01 * ny + a02 * nz, ax1 = a01 * nx + a11 * ny + a12 * nz, ax2 = a02 * nx + a12 * ny + a22 * nz;
+    const double au0 = a00 * u0 + a01 * u1 + a02 * u2, au1 = a01 * u0 + a11 * u1 + a12 * u2, au2 = a02 * u0 + a12 * u1 + a22 * u2;
+    const double aw0 = a00 * w0 + a01 * w1 + a02 * w2, aw1 = a01 * w0 + a11 * w1 + a12 * w2, aw2 = a02 * w0 + a12 * w1 + a22 * w2;
+    const double rho = nx * ax0 + ny * ax1 + nz * ax2;
+    const double p = u0 * au0 + u1 * au1 + u2 * au2, q = w0 * au0 + w1 * au1 + w2 * au2, t = w0 * aw0 + w1 * aw1 + w2 * aw2;
+    // eigenvector (c0, c1) of the smaller eigenvalue of [[p, q], [q, t]], from the row of B - lambda I that does not cancel
+    const double h = 0.5 * (p - t), disc = sqrt(h * h + q * q);
+    if (0.5 * (p + t) - disc < rho) {                            // x is not the smallest eigenvector: the plane holds it
+      double c0, c1;
+      if (h >= 0.0) { c0 = -q; c1 = h + disc; }
+      else          { c0 = disc - h; c1 = -q; }
+      const double cc = c0 * c0 + c1 * c1;
+      if (cc > 0.0) { const double cn = 1.0 / sqrt(cc); c0 *= cn; c1 *= cn; }
+      else          { c0 = 1.0; c1 = 0.0; }                      // rank <= 1: every direction of the plane has eigenvalue 0
+      x0 = c0 * u0 + c1 * w0; x1 = c0 * u1 + c1 * w1; x2 = c0 * u2 + c1 * w2;
+      const double yn = 1.0 / sqrt(x0 * x0 + x1 * x1 + x2 * x2);
+      nx = x0 * yn; ny = x1 * yn; nz = x2 * yn;
+    }
+  }
 }
 #undef DL_ADJ
 
@@ -276,8 +311,17 @@ extern "C" int dl_normals(const float* image4, int64_t image_ss, int32_t S, int3
   if (half_rows == 3 && half_cols == 5)   // the reference's 7x11 window (config_datasets.yaml: every sensor)
     hipLaunchKernelGGL((k_normals<3, 5>), grid, dim3(NTH * NTW), lds, (hipStream_t)stream, image4, image_ss, H, W,
                        half_rows, half_cols, epsilon_range, min_neighbors, normals, (float4*)packed_normals);
-  else
+  else {
+    // Windows with (4 + 2a)(64 + 2b) > 4096 staged pixels -- (15,29) .. (15,31), 66 368 .. 68 544 B -- ask for more dynamic LDS than
+    // the 64 KiB a kernel may use by default: raise this kernel's limit for them (a workgroup may use up to 160 KiB on gfx950).
+    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_normals<-1, -1>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+      (void)hipGetLastError();
+      return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_normals: the device refuses %zu bytes of LDS for the window a=%d b=%d", lds,
+                     half_rows, half_cols);
+    }
     hipLaunchKernelGGL((k_normals<-1, -1>), grid, dim3(NTH * NTW), lds, (hipStream_t)stream, image4, image_ss, H, W,
                        half_rows, half_cols, epsilon_range, min_neighbors, normals, (float4*)packed_normals);
+  }
   return dl_check_launch("dl_normals");
 }

@@ -103,7 +103,16 @@ int dl_project(const float* pts, int64_t pts_cs, int64_t n_cols, const int32_t* 
  *   image4  [S][4][H][W] in (scan stride image_ss elements, channel stride H*W)
  *   normals [S][3][H][W] out (scan stride 3*H*W), zeros where no normal
  *   packed_normals [S][H][W][4] out (may be NULL): (nx,ny,nz,0), pixel-interleaved
- * A pixel is processed iff x != 0 && y != 0 && z != 0 (normal_computation.py:35).
+ * A pixel is processed iff x != 0 && y != 0 && z != 0 (normal_computation.py:35); a neighbour counts iff any of its components is
+ * non-zero, its range is finite and |range - centre range| <= epsilon_range (fp32; equality keeps it); window coordinates are
+ * clamped to the image (edge pixels are duplicated, no wrap); a normal needs min_neighbors such neighbours (the centre included).
+ * min_neighbors < 2 is accepted but leaves the covariance of a single neighbour undefined.
+ *   half_rows 0..15, half_cols 0..31 (a = half_rows, b = half_cols: the window is (2a+1) x (2b+1)); anything else, S, H or W <= 0
+ *   or a null image4 / normals is DL_ERR_INVALID_ARGUMENT before any launch.  Every window in that range runs: the tile staged in
+ *   LDS is (4+2a)(64+2b) pixels of 16 bytes, up to 68 544 B at (15,31), and the entry point raises the kernel's dynamic-LDS limit
+ *   where that exceeds 64 KiB (a device that refuses the raise is DL_ERR_INVALID_ARGUMENT as well, before the launch).
+ *   "Range" is the fp32 value sqrt(fma(z, z, fma(y, y, x * x))): a finite point whose squares overflow fp32 (|coordinate| above
+ *   ~1.8e19) has an infinite range and is an empty pixel.
  */
 int dl_normals(const float* image4, int64_t image_ss, int32_t S, int32_t H, int32_t W,
                int32_t half_rows, int32_t half_cols, float epsilon_range, int32_t min_neighbors,

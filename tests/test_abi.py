@@ -45,6 +45,14 @@ def test_argument_validation_reports_through_last_error():
     assert rc < 0 and b"dl_icp_loss_bwd" in lib.dl_last_error()
     rc = lib.dl_normals(None, 0, 1, 4, 4, 3, 5, 0.5, 10, None, None, None)
     assert rc < 0 and b"null" in lib.dl_last_error()
+    # windows outside the documented range (half_rows 0..15, half_cols 0..31) and empty shapes are refused before any launch: the
+    # pointers are never touched (host memory here), and the text names the offending sizes
+    import ctypes
+    dummy = ctypes.addressof((ctypes.c_float * 4)())
+    for S, H, W, a, b in ((1, 4, 4, 16, 5), (1, 4, 4, 3, 32), (1, 4, 4, -1, 5), (1, 4, 4, 3, -1), (0, 4, 4, 3, 5), (1, 0, 4, 3, 5), (1, 4, 0, 3, 5)):
+        rc = lib.dl_normals(dummy, 48, S, H, W, a, b, 0.5, 10, dummy, None, None)
+        assert rc == -1 and b"dl_normals: bad sizes" in lib.dl_last_error(), (S, H, W, a, b)
+        assert f"a={a} b={b}".encode() in lib.dl_last_error()
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
