@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdelora_hip.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class DeloraHipError(RuntimeError):
@@ -104,6 +104,7 @@ SIGNATURES = {
     "dl_conv2d_wgrad_batch_nhwc_f32": (_i32, [_vp, _i32, _vp, _vp]),
     "dl_conv2d_wgrad_batch_h_workspace_bytes": (_sz, [_vp, _i32]),
     "dl_conv2d_wgrad_batch_nhwc_h": (_i32, [_vp, _i32, _vp, _i32, _vp]),
+    "dl_conv_plan_describe": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_char_p, _sz]),
     "dl_profile_begin": (_i32, [_i32, ctypes.c_char_p]),
     "dl_profile_end": (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "dl_profile_pause": (_i32, [_i32]),
@@ -167,6 +168,19 @@ def profile_end(capacity=512):
     out = [{"name": rows[i].name.decode(), "launches": rows[i].launches, "ms": rows[i].ms, "flop": rows[i].flop, "bytes": rows[i].bytes}
            for i in range(min(n.value, capacity))]
     return out, untimed.value
+
+# ops of dl_conv_plan_describe (DL_PLAN_* of include/delora_hip.h)
+PLAN_CONV, PLAN_DGRAD_STRIDED, PLAN_WINO_CONV, PLAN_WGRAD, PLAN_WGRAD_BATCH, PLAN_WINO_WGRAD, PLAN_WINO_WGRAD_BATCH = range(7)
+
+
+def conv_plan(op, dtype, N, H, W, C, K, ksize=3, sh=1, sw=1, mode=0, cu_count=0):
+    """What the convolution dispatch would launch (``dl_conv_plan_describe``): a list of lines, one per launch,
+    ``"<kernel instantiation> grid=.. block=..[ slabs=n][ splits=n]"``.  ``cu_count`` > 0 needs no GPU."""
+    buf = ctypes.create_string_buffer(4096)
+    check(load().dl_conv_plan_describe(int(op), int(dtype), int(N), int(H), int(W), int(C), int(K), int(ksize), int(sh), int(sw),
+                                       int(mode), int(cu_count), buf, len(buf)), "dl_conv_plan_describe")
+    return buf.value.decode().split("\n")
+
 
 _lib = None
 

@@ -2,6 +2,9 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <cxxabi.h>
 
 #include <atomic>
 #include <map>
@@ -23,6 +26,7 @@ int dl_fail(int code, const char* fmt, ...) {
 
 // Launch errors only: never synchronises (the call stays asynchronous and graph-capturable).
 int dl_check_launch(const char* what) {
+  if (g_dl_plan) return DL_OK;                 // a plan query launched nothing (and may run without a device)
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return dl_fail(DL_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
   return DL_OK;
@@ -138,6 +142,47 @@ extern "C" int64_t dl_wgrad_batch_plan(const int32_t* tiles, const int32_t* chun
       makespan = std::max(makespan, t);
     }
   return makespan;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Plan sink (common.h); the query built on it is plan.hip
+thread_local DlPlanSink* g_dl_plan = nullptr;
+
+static void dl_plan_append(const char* text, size_t n) {
+  DlPlanSink* s = g_dl_plan;
+  if (s->buf && s->len + n + 1 <= s->cap) { memcpy(s->buf + s->len, text, n); s->buf[s->len + n] = 0; }
+  s->len += n;
+}
+
+void dl_plan_record(const char* mangled_tag, dim3 grid, dim3 block) {
+  // "DlKernelTag<&(void k_conv_f32<128, 64, 8, 128, GeomConv<3, 1, 1>, false, 2>(ConvArgs))>" -> the instantiation alone
+  int status = 0;
+  char* full = abi::__cxa_demangle(mangled_tag, nullptr, nullptr, &status);
+  const char* b = full ? full : mangled_tag;
+  if (const char* v = strstr(b, "void ")) b = v + 5;
+  else if (const char* a = strchr(b, '&')) b = a + 1;
+  while (*b == '(') ++b;
+  size_t n = 0;
+  for (int depth = 0; b[n]; ++n) {                       // up to the parameter list (or the tag's closing bracket)
+    if (b[n] == '<') ++depth;
+    else if (b[n] == '>' && --depth < 0) break;
+    else if (b[n] == '(' && depth == 0) break;
+  }
+  if (g_dl_plan->len) dl_plan_append("\n", 1);
+  dl_plan_append(b, n);
+  free(full);
+  char tail[96];
+  const int m = snprintf(tail, sizeof(tail), " grid=%ux%ux%u block=%u", grid.x, grid.y, grid.z, block.x);
+  dl_plan_append(tail, (size_t)m);
+}
+
+void dl_plan_note(const char* fmt, ...) {
+  char text[96] = " ";
+  va_list ap;
+  va_start(ap, fmt);
+  const int m = vsnprintf(text + 1, sizeof(text) - 1, fmt, ap);
+  va_end(ap);
+  if (m > 0) dl_plan_append(text, (size_t)(m < (int)sizeof(text) - 2 ? m + 1 : sizeof(text) - 1));
 }
 
 extern "C" int dl_abi_version(void) { return DL_ABI_VERSION; }

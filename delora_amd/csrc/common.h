@@ -120,10 +120,37 @@ struct DlProfTag {
 };
 bool dl_prof_is_open();
 void dl_prof_events(const DlProfTag& tag, hipEvent_t* e0, hipEvent_t* e1);
+
+// Plan sink (abi.hip; dl_conv_plan_describe of the C ABI): while a sink is installed on the calling thread, the convolution entry
+// points run their whole dispatch -- argument checks, tile choice, slab / split plans -- but every launch is replaced by a record of
+// the kernel instantiation it would have started (the compiler's own name of the function the launch names, demangled from the type
+// of a tag that carries it: the label cannot drift from the code), its grid and block; no HIP call is made, so the query also answers on a machine without a GPU.  Not installed: one
+// thread-local load per launch.
+struct DlPlanSink {
+  char* buf;          // NUL-terminated text, one line per launch
+  size_t cap, len;    // len counts what the full text needs (may exceed cap)
+  int cu_count;       // > 0: stands in for the device's CU count
+};
+extern thread_local DlPlanSink* g_dl_plan;
+void dl_plan_record(const char* mangled_tag, dim3 grid, dim3 block);
+void dl_plan_note(const char* fmt, ...);     // appended to the line of the last recorded launch (split / slab counts)
+#include <typeinfo>
+template <auto KERNEL> struct DlKernelTag {};
+template <auto KERNEL>
+const char* dl_kernel_tag() { return typeid(DlKernelTag<KERNEL>).name(); }
+#define DL_PLAN_NOTE(...) do { if (g_dl_plan) dl_plan_note(__VA_ARGS__); } while (0)
+
 #define DL_LAUNCH(TAG, KERNEL, GRID, BLOCK, STREAM, ...)                                             \
   do {                                                                                                \
+    if (g_dl_plan) { dl_plan_record(dl_kernel_tag<KERNEL>(), GRID, BLOCK); break; }                \
     hipEvent_t dl_e0_ = nullptr, dl_e1_ = nullptr;                                                    \
     if (dl_prof_is_open()) dl_prof_events((TAG), &dl_e0_, &dl_e1_);                                   \
     if (dl_e0_) hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, STREAM, dl_e0_, dl_e1_, 0, __VA_ARGS__); \
     else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, STREAM, __VA_ARGS__);                             \
+  } while (0)
+// the launches that carry no profile tag (seam terms, slab reductions)
+#define DL_LAUNCH_PLAIN(KERNEL, GRID, BLOCK, STREAM, ...)                                            \
+  do {                                                                                                \
+    if (g_dl_plan) { dl_plan_record(dl_kernel_tag<KERNEL>(), GRID, BLOCK); break; }                \
+    hipLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, STREAM, __VA_ARGS__);                                  \
   } while (0)

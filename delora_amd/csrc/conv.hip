@@ -846,7 +846,7 @@ extern "C" int dl_conv2d_dgrad_strided_nhwc_f32(const float* g, const float* w, 
   hipStream_t st = (hipStream_t)stream;
   if (odd_w) {
     const int row_tiles = (H + FX_ROWS - 1) / FX_ROWS;
-    hipLaunchKernelGGL(k_dgrad_oddw_seam, dim3(N * row_tiles, 2, (C + 63) / 64), dim3(CV_THREADS), 0, st, g, w, seam_ws, N, Ho, Wo, K, C, H, stride_h);
+    DL_LAUNCH_PLAIN(k_dgrad_oddw_seam, dim3(N * row_tiles, 2, (C + 63) / 64), dim3(CV_THREADS), st, g, w, seam_ws, N, Ho, Wo, K, C, H, stride_h);
   }
   int rc = 1;
   if (dense) {                                        // 1x1 layer: only phase (0,0) is non-zero; result kept on the grid
@@ -913,8 +913,9 @@ static int launch_wgrad(const float* x, const float* g, float* dw, float* ws, in
   else
     DL_LAUNCH(tag, (k_wgrad_f32<BMK, BNC, PK, SH, SW, KS>), dim3(tiles * nslabs), dim3(CV_THREADS), st, x, g, ws, N,
               H, W, C, K, Ho, Wo, chunks_per_slab, nslabs);
+  DL_PLAN_NOTE("slabs=%d", nslabs);
   const size_t count = (size_t)K * KS * KS * C;
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((count / 4 + CV_THREADS - 1) / CV_THREADS)), dim3(CV_THREADS), 0, st,
+  DL_LAUNCH_PLAIN(k_wgrad_reduce, dim3((unsigned)((count / 4 + CV_THREADS - 1) / CV_THREADS)), dim3(CV_THREADS), st,
                      (const float*)ws, nslabs, count, dw);
   return 0;
 }
@@ -997,6 +998,7 @@ void launch_wgrad_batch(const WgBatchArgs& b, int wgs, const DlProfTag& tag, hip
   }
   if (fast) DL_LAUNCH(tag, (k_wgrad_f32_batch<64, 64, wg_pk(SW, KS), SH, SW, KS, true>), dim3(wgs), dim3(CV_THREADS), st, b);
   else DL_LAUNCH(tag, (k_wgrad_f32_batch<64, 64, wg_pk(SW, KS), SH, SW, KS>), dim3(wgs), dim3(CV_THREADS), st, b);
+  for (int i = 0; i < b.n; ++i) DL_PLAN_NOTE("slabs=%d", b.layer[i].nslabs);
 }
 }  // namespace
 
@@ -1055,6 +1057,6 @@ extern "C" int dl_conv2d_wgrad_batch_nhwc_f32(const dl_wgrad_layer* layers, int3
     ++r.n;
   }
   r.first_block[r.n] = blocks;
-  if (r.n) hipLaunchKernelGGL(k_wgrad_reduce_batch, dim3(blocks), dim3(CV_THREADS), 0, st, r);
+  if (r.n) DL_LAUNCH_PLAIN(k_wgrad_reduce_batch, dim3(blocks), dim3(CV_THREADS), st, r);
   return dl_check_launch("dl_conv2d_wgrad_batch_nhwc_f32");
 }

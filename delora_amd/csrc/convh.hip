@@ -782,8 +782,8 @@ extern "C" int dl_conv2d_dgrad_strided_nhwc_h(const void* g, const void* w, void
   hipStream_t st = (hipStream_t)stream;
   if (odd_w) {
     const dim3 grid(N * ((H + FXH_ROWS - 1) / FXH_ROWS), 2, (C + 63) / 64);
-    if (dtype == DL_DTYPE_F16) hipLaunchKernelGGL(k_dgrad_oddw_seam_h<true>, grid, dim3(256), 0, st, (const u16*)g, (const u16*)w, seam_ws, N, Ho, Wo, K, C, H, stride_h);
-    else hipLaunchKernelGGL(k_dgrad_oddw_seam_h<false>, grid, dim3(256), 0, st, (const u16*)g, (const u16*)w, seam_ws, N, Ho, Wo, K, C, H, stride_h);
+    if (dtype == DL_DTYPE_F16) DL_LAUNCH_PLAIN(k_dgrad_oddw_seam_h<true>, grid, dim3(256), st, (const u16*)g, (const u16*)w, seam_ws, N, Ho, Wo, K, C, H, stride_h);
+    else DL_LAUNCH_PLAIN(k_dgrad_oddw_seam_h<false>, grid, dim3(256), st, (const u16*)g, (const u16*)w, seam_ws, N, Ho, Wo, K, C, H, stride_h);
   }
   const int rc = dtype == DL_DTYPE_F16 ? dgrad_strided_h<true>(a, ksize, stride_h, stride_w, dense, st)
                                        : dgrad_strided_h<false>(a, ksize, stride_h, stride_w, dense, st);

@@ -349,6 +349,7 @@ static void launch_wgradh(const WgradHArgs& a, const WgradHPlan& p, hipStream_t 
   const DlProfTag tag{"k_wgradh", "wgrad", a.N, a.H, a.W, a.C, a.K, KS, SH, SW, 2.0 * a.N * a.Ho * a.Wo * (double)a.K * a.C * KS * KS,
                       2.0 * ((double)a.N * a.H * a.W * a.C + (double)a.N * a.Ho * a.Wo * a.K) + 4.0 * a.K * KS * KS * a.C};
   DL_LAUNCH(tag, (k_wgradh<F16, BMK, PK, 2, SH, SW, KS>), dim3(p.tiles * p.nslabs), dim3(64 * (BMK / 32) * 2), st, a);
+  DL_PLAN_NOTE("slabs=%d", p.nslabs);
 }
 
 template <bool F16, int SH, int SW, int KS>
@@ -391,7 +392,7 @@ extern "C" int dl_conv2d_wgrad_nhwc_h(const void* x, const void* g, float* dw, v
                                        : wgradh_dispatch<false>(a, p, ksize, stride_h, stride_w, st);
   if (rc) return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_wgrad_nhwc_h: no kernel for this shape");
   const size_t count = (size_t)K * ksize * ksize * C;
-  hipLaunchKernelGGL(k_wgradh_reduce, dim3((unsigned)((count / 4 + 255) / 256)), dim3(256), 0, st, (const float*)workspace, p.nslabs, count, dw);
+  DL_LAUNCH_PLAIN(k_wgradh_reduce, dim3((unsigned)((count / 4 + 255) / 256)), dim3(256), st, (const float*)workspace, p.nslabs, count, dw);
   return dl_check_launch("dl_conv2d_wgrad_nhwc_h");
 }
 
@@ -455,6 +456,7 @@ int wgradh_batch_plan(const dl_wgrad_h_layer* L, int n, std::vector<WgradHItem>&
 template <bool F16, int BMK, int PK, int SH, int SW, int KS>
 void launch_wgradh_batch(const WgradHBatchArgs& b, int wgs, const DlProfTag& tag, hipStream_t st) {
   DL_LAUNCH(tag, (k_wgradh_batch<F16, BMK, PK, 2, SH, SW, KS>), dim3(wgs), dim3(64 * (BMK / 32) * 2), st, b);
+  for (int i = 0; i < b.n; ++i) DL_PLAN_NOTE("slabs=%d", b.layer[i].nslabs);
 }
 template <bool F16, int SH, int SW, int KS>
 int wgradh_batch_geom(const WgradHBatchArgs& b, int wgs, int bmk, int pk, const DlProfTag& tag, hipStream_t st) {
@@ -535,6 +537,6 @@ extern "C" int dl_conv2d_wgrad_batch_nhwc_h(const dl_wgrad_h_layer* layers, int3
     ++r.n;
   }
   r.first_block[r.n] = blocks;
-  if (r.n) hipLaunchKernelGGL(k_wgradh_reduce_batch, dim3(blocks), dim3(256), 0, st, r);
+  if (r.n) DL_LAUNCH_PLAIN(k_wgradh_reduce_batch, dim3(blocks), dim3(256), st, r);
   return dl_check_launch("dl_conv2d_wgrad_batch_nhwc_h");
 }

@@ -1433,6 +1433,7 @@ __device__ __forceinline__ void wino_wgrad_out_body(const float* __restrict__ uu
 // CU count of the current device (the persistent grid's size), cached per device id
 #include <atomic>
 static int wn_cu_count() {
+  if (g_dl_plan && g_dl_plan->cu_count > 0) return g_dl_plan->cu_count;      // dl_conv_plan_describe: the caller's CU count
   static std::atomic<int> cache[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
@@ -1482,10 +1483,11 @@ extern "C" int dl_wino_wgrad3x3_nhwc_f32(const float* x, const float* g, float* 
                       4.0 * ((double)N * H * W * (C + K) + 9.0 * C * K)};
   if (ww_exact(H, W)) DL_LAUNCH(tag, k_wino_wgrad<false>, dim3(tiles * nslabs), dim3(WW_THREADS), st, a);
   else DL_LAUNCH(tag, k_wino_wgrad<true>, dim3(tiles * nslabs), dim3(WW_THREADS), st, a);
+  DL_PLAN_NOTE("slabs=%d", nslabs);
   const size_t count4 = (size_t)16 * K * C / 4;
   float* usum = ws + (size_t)nslabs * 16 * K * C;
-  hipLaunchKernelGGL(k_wino_wgrad_sum, dim3((unsigned)((count4 + 255) / 256)), dim3(256), 0, st, (const float*)ws, nslabs, count4, usum);
-  hipLaunchKernelGGL(k_wino_wgrad_out, dim3((unsigned)(((size_t)K * C + 255) / 256)), dim3(256), 0, st, (const float*)usum, K, C, dw);
+  DL_LAUNCH_PLAIN(k_wino_wgrad_sum, dim3((unsigned)((count4 + 255) / 256)), dim3(256), st, (const float*)ws, nslabs, count4, usum);
+  DL_LAUNCH_PLAIN(k_wino_wgrad_out, dim3((unsigned)(((size_t)K * C + 255) / 256)), dim3(256), st, (const float*)usum, K, C, dw);
   return dl_check_launch("dl_wino_wgrad3x3_nhwc_f32");
 }
 
@@ -1576,6 +1578,7 @@ extern "C" int dl_wino_wgrad3x3_batch_nhwc_f32(const dl_wgrad_layer* layers, int
     const DlProfTag tag{"k_wino_wgrad", b.n > 1 ? "wgrad-batch" : "wgrad", f.N, f.H, f.W, f.C, f.K, 3, 1, 1, flop, bytes};
     if (rag) DL_LAUNCH(tag, k_wino_wgrad_batch<true>, dim3(wgs), dim3(WW_THREADS), st, b);
     else DL_LAUNCH(tag, k_wino_wgrad_batch<false>, dim3(wgs), dim3(WW_THREADS), st, b);
+    for (int i = 0; i < b.n; ++i) DL_PLAN_NOTE("slabs=%d", b.layer[i].nslabs);
   }
   WWPostArgs sum{}, out{};
   int sum_blocks = 0, out_blocks = 0;
@@ -1592,8 +1595,8 @@ extern "C" int dl_wino_wgrad3x3_batch_nhwc_f32(const dl_wgrad_layer* layers, int
     ++out.n;
   }
   sum.first_block[sum.n] = sum_blocks; out.first_block[out.n] = out_blocks;
-  if (sum.n) hipLaunchKernelGGL(k_wino_wgrad_sum_batch, dim3(sum_blocks), dim3(256), 0, st, sum);
-  hipLaunchKernelGGL(k_wino_wgrad_out_batch, dim3(out_blocks), dim3(256), 0, st, out);
+  if (sum.n) DL_LAUNCH_PLAIN(k_wino_wgrad_sum_batch, dim3(sum_blocks), dim3(256), st, sum);
+  DL_LAUNCH_PLAIN(k_wino_wgrad_out_batch, dim3(out_blocks), dim3(256), st, out);
   return dl_check_launch("dl_wino_wgrad3x3_batch_nhwc_f32");
 }
 
@@ -1693,6 +1696,7 @@ extern "C" int dl_wino_conv3x3_nhwc_f32(const float* x, const float* u, float* y
       case 8: DL_LAUNCH(tag, (k_wino_conv<8, true, true>), grid, dim3(WN_THREADS), st, a); break;
       default: DL_LAUNCH(tag, (k_wino_conv<4, true, true>), grid, dim3(WN_THREADS), st, a); break;
     }
+    DL_PLAN_NOTE("splits=%d", p.splits);
     const size_t count4 = (size_t)N * H * W * K / 4;
     const DlProfTag tag2{"k_wino_split_sum", "conv", N, H, W, C, K, 3, 1, 1, 0.0, 4.0 * (double)N * H * W * K * (p.splits + 1)};
     DL_LAUNCH(tag2, k_wino_split_sum, dim3((unsigned)((count4 + 255) / 256)), dim3(256), st, (const float*)workspace, p.splits, count4, y, add,

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DL_ABI_VERSION 9   /* 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
+#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
 
 typedef void* dl_stream;
 
@@ -296,6 +296,11 @@ int dl_ring_act_pool_pad_bwd_t(const void* grad_out, const void* y, const int8_t
  *   divide -- the reference's shipped 64x720 image has feature maps 180, 90, 45 and 23 pixels wide (config/config_datasets.yaml:21)
  *   -- odd sizes included.  Channels must tile: K % 64 == 0, C % 8 == 0 (DL_ERR_UNSUPPORTED otherwise; the caller then uses its
  *   library convolution).
+ *   ALIGNMENT (every entry point of the convolution families, fp32, Winograd and half precision alike): each tensor, weight, seam and
+ *   workspace pointer must be 16-byte aligned -- operands move as 16-byte vectors (four fp32 / eight half values; the LDS DMA copies
+ *   16 bytes per lane) and the channel counts above keep every pixel's row of channels a multiple of 16 bytes, so an aligned base
+ *   keeps every access aligned.  Nothing more is assumed: a base 16 bytes past a 256-byte boundary is as good as an allocator's.
+ *   The kernels write only inside the tensors they are given (overhanging tiles are masked in the epilogue) and read only inside them.
  */
 #define DL_CONV_ADD  1u
 #define DL_CONV_ACT  2u
@@ -553,6 +558,31 @@ int dl_quat_to_T_bwd(const float* quaternion, const float* grad_T, int32_t B, fl
 /* Global average pooling of a channels-last feature map (reference resnet_modified.py: avgpool + flatten before fc):
  * x [N][P][C] (P = H*W pixels) -> y [N][C]; fixed summation order; C % 4 == 0. */
 int dl_mean_hw_nhwc_f32(const float* x, int32_t N, int32_t P, int32_t C, float* y, dl_stream stream);
+
+/*
+ * What the convolution dispatch would launch (for tests and tools; host only, nothing is enqueued): runs the matching entry point's
+ * own code -- argument checks, tile choice, slab / split plans -- with every launch replaced by a record, and writes one line per
+ * launch into buf:   <kernel instantiation> grid=<x>x<y>x<z> block=<threads>[ slabs=<n> ...][ splits=<n>]
+ * e.g. "k_wino_conv<32, false, true> grid=64x1x1 block=512 splits=4".  The instantiation is the compiler's own spelling of the
+ * template the launch names, so the text cannot drift from the dispatch.
+ *   op      DL_PLAN_*: CONV (dl_conv2d_nhwc_f32 / _h; mode = transposed), DGRAD_STRIDED (dl_conv2d_dgrad_strided_nhwc_f32 / _h; mode =
+ *           dense; H, W = the layer's input image, C its input and K its output channels), WINO_CONV (dl_wino_conv3x3_nhwc_f32;
+ *           mode 0 = with a workspace, 1 = workspace NULL), WGRAD / WGRAD_BATCH (dl_conv2d_wgrad_nhwc_f32 / _h and a one-layer
+ *           dl_conv2d_wgrad_batch_*), WINO_WGRAD / WINO_WGRAD_BATCH (dl_wino_wgrad3x3_nhwc_f32 and its one-layer batch form)
+ *   dtype   DL_DTYPE_F32 selects the fp32 entry point, _F16 / _BF16 the half-precision one (the Winograd ops are fp32 only)
+ *   cu_count > 0 stands in for the device's CU count (the Winograd split plan depends on it): the query then needs no GPU;
+ *           0 asks the current device (256 where there is none).
+ * Returns the entry point's own status (dl_last_error has its text), DL_ERR_INVALID_ARGUMENT when buf is too small.
+ */
+#define DL_PLAN_CONV 0
+#define DL_PLAN_DGRAD_STRIDED 1
+#define DL_PLAN_WINO_CONV 2
+#define DL_PLAN_WGRAD 3
+#define DL_PLAN_WGRAD_BATCH 4
+#define DL_PLAN_WINO_WGRAD 5
+#define DL_PLAN_WINO_WGRAD_BATCH 6
+int dl_conv_plan_describe(int32_t op, int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t K, int32_t ksize,
+                          int32_t stride_h, int32_t stride_w, int32_t mode, int32_t cu_count, char* buf, size_t buf_bytes);
 
 /* Measurement aid (bench.py, tools/): between dl_profile_begin and dl_profile_end every launch of the convolution families
  * (fp32 direct / Winograd / weight gradient, half-precision forward / weight gradient) carries its own begin / end timestamps

@@ -50,8 +50,8 @@ def test_entry_points_are_declared_exported_and_bound():
     assert _lib.SIGNATURES["dl_nn_list_tree_bytes"][0] is ctypes.c_size_t
     assert _lib.SIGNATURES["dl_nn_list_query_workspace_bytes"][0] is ctypes.c_size_t
     assert len(_lib.SIGNATURES["dl_nn_list_build"][1]) == 5 and len(_lib.SIGNATURES["dl_nn_list_query"][1]) == 10
-    assert lib.dl_abi_version() == 9 == _lib.ABI_VERSION
-    assert "#define DL_ABI_VERSION 9" in open(os.path.join(ROOT, "include", "delora_hip.h")).read()
+    assert lib.dl_abi_version() == 10 == _lib.ABI_VERSION
+    assert "#define DL_ABI_VERSION 10 " in open(os.path.join(ROOT, "include", "delora_hip.h")).read()
 
 
 COUNTS = (0, 1, 2, 63, 64, 65, 1000, 2048, 2049, 4096, 4097, 32768, 70001, 131072, 262144, 262145, 1 << 24, (1 << 24) + 1, MAX_POINTS)
