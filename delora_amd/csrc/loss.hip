@@ -410,6 +410,7 @@ extern "C" int dl_icp_loss_partial_timed(const float* src_image4, int64_t src_ss
   if ((H * W) % 4 == 0 && ((src_ss | srcn_ss | match_ss) % 4 ||
                            (((uintptr_t)src_image4 | (uintptr_t)src_normals | (uintptr_t)match | (uintptr_t)nn_pix) & 15)))
     return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_icp_loss_partial: planes and nn_pix must be 16-byte aligned");
+  if ((uintptr_t)workspace & 15) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_icp_loss_partial: workspace must be 16-byte aligned");
   if ((flags & DL_LOSS_PO2PO_ALONE) && (flags & (DL_LOSS_POINT_TO_PLANE | DL_LOSS_PLANE_TO_PLANE)))
     return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_icp_loss_partial: po2po_alone excludes the point-to-plane / plane-to-plane terms "
                                             "(the reference has no pair lists for them in this mode, icp_losses.py:36-45,135-146)");
@@ -447,6 +448,7 @@ extern "C" int dl_icp_loss_reduce(const void* workspace, int32_t B, int32_t H, i
                                   float* loss_terms, int32_t* pair_counts, float* grad_terms, dl_stream stream) {
   if (!workspace || !loss_terms || !pair_counts || !grad_terms || B <= 0 || H <= 0 || W <= 0)
     return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_icp_loss_reduce: bad argument");
+  if ((uintptr_t)workspace & 15) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_icp_loss_reduce: workspace must be 16-byte aligned");
   LossOut out{loss_terms, pair_counts, grad_terms, flags};
   hipLaunchKernelGGL(k_icp_reduce, dim3(B), dim3(DL_BLOCK), 0, (hipStream_t)stream, (const float*)workspace,
                      loss_rows(H * W), out);

@@ -42,7 +42,7 @@ __global__ void k_quat_to_T_bwd(const float* __restrict__ q, const float* __rest
   const float dz = 2.0f * (x * (g02 + g20) + y * (g12 + g21) + w * (g10 - g01)) - 4.0f * z * (g00 + g11);
   const float dw = 2.0f * (x * (g21 - g12) + y * (g02 - g20) + z * (g10 - g01));
   float ox, oy, oz, ow;
-  if (n > eps) {                                           // d(q/|q|)/dq = (I - u u^T) / |q|
+  if (n >= eps) {                                          // d(q/|q|)/dq = (I - u u^T) / |q|; at |q| == eps too, as clamp_min's gradient
     const float s = x * dx + y * dy + z * dz + w * dw;
     ox = (dx - x * s) / den; oy = (dy - y * s) / den; oz = (dz - z * s) / den; ow = (dw - w * s) / den;
   } else {                                                 // clamped: q / eps

@@ -162,6 +162,15 @@ size_t dl_icp_loss_workspace_bytes(int32_t B, int32_t H, int32_t W);
  *                          NaN when an enabled term has no pairs, as torch's MSELoss of an empty set)
  *   pair_counts[B][2]      out: pairs with normals (K), pairs without normals (K', po2po)
  *   grad_terms [B][3][12]  out: d loss_term / d T[:3,:4] (row-major 3x4), correspondences held fixed
+ * Masking is MULTIPLICATIVE: every pixel's residuals are formed and then multiplied by 0 or 1 (nn_pix < 0, a missing normal on
+ * either side and po2po_alone select the factor), so that no load waits for a branch.  The operands at pixels that do not count
+ * -- all thirteen planes where nn_pix < 0, the normals of a pair whose partner has none -- must therefore be FINITE: an inf or
+ * NaN there turns the sample's sums into NaN (0 * inf), any finite value contributes an exact zero.  dl_nn_correspond writes zeros
+ * into match where it writes nn_pix = -1, and dl_project / dl_normals write zeros into empty source pixels.  A ragged last chunk
+ * re-reads pixel 0 of every plane under a zero factor, so pixel 0 must be finite as well.  T itself may be anything: a non-finite
+ * pose stays in its own sample, the other samples' outputs do not change by a bit.
+ *   workspace              dl_icp_loss_workspace_bytes(B, H, W) bytes, 16-byte aligned whatever H*W is (the reduction reads the partial
+ *                          rows with 16-byte loads); a workspace that is not is DL_ERR_INVALID_ARGUMENT before any launch
  */
 int dl_icp_loss_fwd(const float* src_image4, int64_t src_ss, const float* src_normals, int64_t srcn_ss,
                     const float* match, int64_t match_ss, const int32_t* nn_pix, const float* T, int32_t B, int32_t H, int32_t W,

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import util
+from tests.tail_ref import torch_loss_terms
 from tests.util import orc
 
 pytestmark = pytest.mark.gpu
@@ -715,35 +716,8 @@ def test_normals_known_answer_plane():
     assert has.mean() > 0.9 and np.allclose(n[has], [-1.0, 0.0, 0.0], atol=2e-3)
 
 
-def _torch_loss_terms(T, src, src_n, tgt, tgt_n, nn, mode, p2p):
-    """The three loss modules as plain fp32 torch ops on the device (icp_losses.py:102-121,168-240 with the gathers the
-    reference performs), differentiable with respect to T -- the full-size counterpart of the CPU oracle."""
-    rows = []
-    for b in range(src.shape[0]):
-        idx = nn[b].reshape(-1).long()
-        valid = idx >= 0
-        idx = idx.clamp(min=0)
-        p, n = src[b, :3].reshape(3, -1), src_n[b].reshape(3, -1)
-        pt, nt = tgt[b, :3].reshape(3, -1)[:, idx], tgt_n[b].reshape(3, -1)[:, idx]
-        R, t = T[b, :3, :3], T[b, :3, 3:4]
-        q, rn = R @ p + t, R @ n
-        has_s, has_t = (n != 0).any(dim=0), (nt != 0).any(dim=0)
-        m = valid & has_s & has_t
-        K = m.sum()
-        r = ((q - pt) * nt).sum(dim=0)
-        po2pl = (r[m] ** 2).sum() / K
-        if mode == "linear":
-            pl2pl = ((1.0 - (rn * nt).sum(dim=0))[m] ** 2).sum() / K
-        else:
-            pl2pl = ((rn - nt)[:, m] ** 2).sum() / K
-        po2po = torch.zeros((), device=src.device)
-        K2 = torch.zeros((), device=src.device)
-        if p2p:
-            m2 = valid & ~has_s & ~has_t
-            K2 = m2.sum()
-            po2po = ((q - pt)[:, m2] ** 2).sum() / (3 * K2)
-        rows.append((torch.stack((po2po, po2pl, pl2pl)), int(K), int(K2)))
-    return torch.stack([r[0] for r in rows]), [r[1] for r in rows], [r[2] for r in rows]
+# the three loss modules as plain torch ops, differentiable with respect to T: shared with the float64 host tests (tests/tail_ref.py)
+_torch_loss_terms = torch_loss_terms
 
 
 @pytest.mark.parametrize("mode,p2p", [("squared", False), ("linear", True)])
