@@ -156,6 +156,8 @@ extern "C" int dl_project(const float* pts, int64_t pts_cs, int64_t n_cols, cons
                    sensor->H, sensor->W, max_n, (long long)n_cols, (long long)pts_cs);
   if (C > 3 && !aux) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_project: C=%d needs an aux image", C);
   if (packed_aux && C < 6) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_project: packed_aux needs C >= 6 (got %d)", C);
+  // the staging records behind the key plane are read and written as float4
+  if ((uintptr_t)workspace & 15) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_project: workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const SensorK sen = make_sensor(sensor);
   // workspace = key plane [S][H*W] uint64 | staging records [n_cols] float4 (x,y,z,range) | [n_cols] float4 (channels 3..5) if C > 3

@@ -85,9 +85,21 @@ size_t dl_project_workspace_bytes(int32_t S, int32_t H, int32_t W, int64_t n_col
  *   packed   [S][H][W][4]  out (may be NULL): x,y,z,range of the winner, pixel-interleaved
  *   packed_aux [S][H][W][4] out (may be NULL; needs C >= 6): channels 3..5 of the winner + 0 (stored normals)
  *   pix2pt   [S][H][W]     out: index of the winning point relative to its scan start, -1 if empty
- *   workspace dl_project_workspace_bytes(S,H,W,n_cols,C) bytes of scratch, 16-byte aligned
+ *   workspace dl_project_workspace_bytes(S,H,W,n_cols,C) bytes of scratch, 16-byte aligned (a misaligned one is refused
+ *                          with DL_ERR_INVALID_ARGUMENT before any launch)
  *   kept     [S]           out (may be NULL): number of occupied pixels per scan
- *   uvr      [3][pts_cs]   out (may be NULL): fp32 u, v and range of EVERY input point, input order
+ *   uvr      [3][pts_cs]   out (may be NULL): fp32 u, v and range of EVERY input point, input order; only the columns
+ *                          offs[0]..offs[S]) of each plane are written
+ * The contract, bit for bit (tests/project_ref.py is its plain restatement):
+ *   range = sqrt(fma(z,z, fma(y,y, x*x))) and norm2 = sqrt(fma(y,y, x*x)), every step correctly rounded to fp32; a point whose
+ *     squares overflow has range +inf: it still votes and loses to every finite point of its pixel;
+ *   a = fp32(atan2(y, x)), e = fp32(atan2(z, norm2)) evaluated in fp64 and rounded once; u = ((a - fp32(hfov0)) / fp32(hfov1 - hfov0))
+ *     * fp32(W-1) in fp32, v likewise; the pixel is rint() of them, half to even;
+ *   a point is inside iff 0 <= rint(u) <= W-1 and 0 <= rint(v) <= H-1: a coordinate that rounds to -0.0 counts as pixel 0, a NaN
+ *     coordinate is outside;
+ *   the winner of a pixel is the point with the smallest (uint32 bit pattern of the range, index within the scan);
+ *   empty pixels hold +0.0 in every image and -1 in pix2pt; packed_aux.w is +0.0;
+ *   max_n only sizes the grid: any value >= the largest scan length gives the same result.
  */
 int dl_project(const float* pts, int64_t pts_cs, int64_t n_cols, const int32_t* offs, int32_t S, int32_t C,
                int32_t max_n, const dl_sensor* sensor, float* image4, float* aux, float* packed,
