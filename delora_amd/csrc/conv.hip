@@ -33,6 +33,23 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// Operands are fetched through buffer descriptors (buffer_load_dwordx4 v, v_off, s[rsrc], s_off offen): the per-lane byte offset of a
+// staged item is one register computed once per tile, the advance from chunk to chunk is the scalar offset, and an item that must read
+// zeros (a row above / below the image, a column beside a pass that does not wrap, a surplus pixel) carries an offset the descriptor's
+// range check rejects -- the load then returns exact zeros and touches no memory, whatever the tensor holds.  A vector instruction next
+// to an fp32 MFMA costs matrix time, a scalar one almost none: the chunk loops hold no address arithmetic on the VALU.
+// One descriptor spans one image (or the weight tensor), so every offset is below 2^32 (the entry points check the sizes).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t cv_rsrc(const float* base, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ f32x4 cv_ld16(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, (int)soff, 0));
+}
+// a per-lane offset that no descriptor accepts: the entry points keep an image and the weights below 2 GiB, so it lies behind every
+// descriptor's end, and its sum with a scalar offset (below the descriptor's size) does not wrap 32 bits -- the zero rows hold whether
+// or not the range check adds the scalar offset
+#define CV_ZERO_OFF 0x80000000u
+
 #define CV_THREADS 256
 #define CV_EPI_ADD 1u    // v += add[pixel][k]
 #define CV_EPI_ACT 2u    // v = act(v)
@@ -97,7 +114,13 @@ __global__ __launch_bounds__(CV_THREADS, CV_MINWAVES) void k_conv_f32(ConvArgs a
   static_assert(TAPS > 0, "a stride phase without taps has no launch");
   static_assert((S / 4) % 2 == 1, "pixel stride must be 4*odd floats");
   constexpr int EPW = WN * 32, ES = EPW + 4;        // epilogue staging: floats per pixel row (+4: the halves hit different banks)
-  constexpr int LDS_FLOATS = IN_FLOATS + W_FLOATS > 4 * 32 * ES ? IN_FLOATS + W_FLOATS : 4 * 32 * ES;
+  // The 256 x 128-pixel tile with transposed weights and 8-channel chunks (the direct input gradient of the stride-1 3x3 layers below 256
+  // channels) is held at two workgroups per CU by its LDS size (a third of the CU's 160 KB, rounded up): its registers admit a third
+  // one, and the 1024 tiles of the network's shapes then run as 768 + 256 instead of 512 + 512 -- measured 9-12 % slower
+  // (profiles/direct_addr_harness.txt)
+  constexpr int LDS_HOLD = (BM == 256 && TW == 128 && CK == 8 && BT) ? 160 * 1024 / 3 / 4 + 16 : 0;
+  constexpr int LDS_USED = IN_FLOATS + W_FLOATS > 4 * 32 * ES ? IN_FLOATS + W_FLOATS : 4 * 32 * ES;
+  constexpr int LDS_FLOATS = LDS_USED > LDS_HOLD ? LDS_USED : LDS_HOLD;
   __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
   float* in_lds = lds;
   float* w_lds = lds + IN_FLOATS;
@@ -106,8 +129,8 @@ __global__ __launch_bounds__(CV_THREADS, CV_MINWAVES) void k_conv_f32(ConvArgs a
   const int li = lane & 31, half = lane >> 5;
   const int wm = wave / WGN, wn = wave % WGN;
   const int KT = a.K / BN;
-  // images that do not tile: the last tile of a row / column hangs over the edge -- its surplus pixels compute on wrapped (valid)
-  // addresses and are not stored
+  // images that do not tile: the last tile of a row / column hangs over the edge -- its surplus pixels compute on wrapped columns
+  // (or, more than one image width out, on zeros) and are not stored
   const int tiles_w = (a.Wo + TW - 1) / TW, tiles_h = (a.Ho + TH - 1) / TH;
   const int ntiles = a.N * tiles_h * tiles_w * KT;
   const int t = cv_xcd_swizzle(blockIdx.x, ntiles);
@@ -120,10 +143,14 @@ __global__ __launch_bounds__(CV_THREADS, CV_MINWAVES) void k_conv_f32(ConvArgs a
   const int h_base = ho0 * SH + G::H0, w_base = wo0 * SW + G::W0;
   const float* xn = a.x + (size_t)n * a.H * a.W * a.C;
 
-  // chunk-invariant staging offsets (element offsets relative to xn / a.w, without the channel chunk).  Item ids beyond
+  // chunk-invariant staging offsets (byte offsets relative to xn / a.w, without the channel chunk).  Item ids beyond
   // the tile are clamped to the last item: those threads load and store the same 16 bytes as its owner, which keeps the
   // staging code free of branches (hipcc otherwise sinks each load into its conditional store and serialises them).
-  int in_g[NI_IT], in_l[NI_IT];
+  const unsigned x_bytes = (unsigned)(a.H * a.W * a.C) * 4u, w_bytes = (unsigned)(a.K * a.C * G::WTAPS) * 4u;
+  const __amdgpu_buffer_rsrc_t x_rs = cv_rsrc(xn, x_bytes), w_rs = cv_rsrc(a.w, w_bytes);
+  const unsigned x_zero = CV_ZERO_OFF;
+  unsigned in_g[NI_IT];
+  int in_l[NI_IT];
 #pragma unroll
   for (int it = 0; it < NI_IT; ++it) {
     const int q = min(tid + it * CV_THREADS, NI - 1);
@@ -132,25 +159,29 @@ __global__ __launch_bounds__(CV_THREADS, CV_MINWAVES) void k_conv_f32(ConvArgs a
     const int h = h_base + row;
     int w = w_base + col;
     const bool col_in = w >= 0 && w < a.W;
-    w %= a.W;                                      // (a full modulo: the surplus columns of an overhanging tile lie beyond 2W)
+    // one wrap each way, no modulo: a pixel that is stored (wo < Wo) reads columns -1 .. W only -- (Wo - 1) * SW + EW - 1 + W0 <= W for
+    // every geometry.  Columns further out (an overhanging tile reaches beyond 2W on narrow images) feed surplus pixels alone, which
+    // are not stored: they read zeros.
     w = w < 0 ? w + a.W : w;
+    w = w >= a.W ? w - a.W : w;
     in_l[it] = pc * S + c4 * 4;
-    // -1: a zero row above / below the image (or, without wrap-around, a zero column beside it)
-    in_g[it] = (h >= 0 && h < a.H && (a.wrap || col_in)) ? (h * a.W + w) * a.C + c4 * 4 : -1;
+    // x_zero: a zero row above / below the image (or, without wrap-around, a zero column beside it)
+    in_g[it] = (h >= 0 && h < a.H && (a.wrap ? w < a.W : col_in)) ? (unsigned)((h * a.W + w) * a.C + c4 * 4) * 4u : x_zero;
   }
-  int w_g[NW_IT], w_l[NW_IT];
+  unsigned w_g[NW_IT];
+  int w_l[NW_IT];
 #pragma unroll
   for (int it = 0; it < NW_IT; ++it) {
     const int q = min(tid + it * CV_THREADS, NW - 1);
     if (!BT) {
       const int c4 = q % C4, t2 = q / C4;
       const int tap = t2 % TAPS, kk = t2 / TAPS;
-      w_g[it] = ((k0 + kk) * G::WTAPS + G::wt(tap)) * a.C + c4 * 4;
+      w_g[it] = (unsigned)(((k0 + kk) * G::WTAPS + G::wt(tap)) * a.C + c4 * 4) * 4u;   // + c0 * 4 per chunk
       w_l[it] = (tap * BN + kk) * S + c4 * 4;
     } else {
       const int co4 = q % (BN / 4), t2 = q / (BN / 4);
       const int tap = t2 % TAPS, kr = t2 / TAPS;
-      w_g[it] = (kr * G::WTAPS + G::wt(tap)) * a.K + k0 + co4 * 4;        // + c0 * WTAPS * K per chunk
+      w_g[it] = (unsigned)((kr * G::WTAPS + G::wt(tap)) * a.K + k0 + co4 * 4) * 4u;        // + c0 * WTAPS * K * 4 per chunk
       w_l[it] = (tap * CK + kr) * BN + co4 * 4;
     }
   }
@@ -172,23 +203,14 @@ __global__ __launch_bounds__(CV_THREADS, CV_MINWAVES) void k_conv_f32(ConvArgs a
     a_off[mi] = ((th * SH) * RW + tw * SW) * S + half * 4;
   }
 
-#ifdef CV_OLD_STAGE
-#define CV_LOADV(C0) f32x4 v = {0.f, 0.f, 0.f, 0.f}; if (in) v = *reinterpret_cast<const f32x4*>(xn + in_g[it] + (C0));
-#else
-#define CV_LOADV(C0) const f32x4 v = *reinterpret_cast<const f32x4*>(xn + (in ? in_g[it] + (C0) : 0));
-#endif
   f32x4 in_r[NI_IT], w_r[NW_IT];     // native vectors (HIP's float4 struct arrays end up in scratch here)
   // (macros, not lambdas: arrays captured by reference keep hipcc from promoting them to registers)
+  // the range check, not a multiply or a select, makes the zero rows: a NaN at element 0 must not leak into them
 #define CV_FETCH(C0)                                                                                                      \
   {                                                                                                                       \
-    _Pragma("unroll") for (int it = 0; it < NI_IT; ++it) {                                                                \
-      const bool in = in_g[it] >= 0;                                                                                      \
-      CV_LOADV(C0)                                                                                                        \
-      /* select, not multiply: a NaN at element 0 must not leak into the zero rows */                                     \
-      in_r[it] = in ? v : (f32x4){0.f, 0.f, 0.f, 0.f};                                                                    \
-    }                                                                                                                     \
-    _Pragma("unroll") for (int it = 0; it < NW_IT; ++it) w_r[it] = *reinterpret_cast<const f32x4*>(                       \
-        a.w + (BT ? (size_t)w_g[it] + (size_t)(C0) * G::WTAPS * a.K : (size_t)w_g[it] + (C0)));                               \
+    const unsigned xs_ = (unsigned)(C0) * 4u, ws_ = BT ? (unsigned)((C0) * G::WTAPS * a.K) * 4u : xs_;    /* scalar */      \
+    _Pragma("unroll") for (int it = 0; it < NI_IT; ++it) in_r[it] = cv_ld16(x_rs, in_g[it], xs_);                         \
+    _Pragma("unroll") for (int it = 0; it < NW_IT; ++it) w_r[it] = cv_ld16(w_rs, w_g[it], ws_);                           \
   }
 #define CV_STAGE()                                                                                                        \
   {                                                                                                                       \
@@ -291,7 +313,9 @@ __global__ __launch_bounds__(CV_THREADS, CV_MINWAVES) void k_conv_f32(ConvArgs a
   // activation and 16-byte stores of whole 128/256-byte channel rows.
   __syncthreads();                                       // every wave is done with the last chunk's fragments
   float* ep = lds + wave * (32 * ES);
-  const size_t out_n = (size_t)n * a.Hout * a.Wout, grid_n = (size_t)n * a.Ho * a.Wo;
+  // (32-bit element offsets: the entry points reject tensors of 2^31 elements and more)
+  const unsigned out_n = (unsigned)(n * a.Hout * a.Wout), grid_n = (unsigned)(n * a.Ho * a.Wo);
+  const unsigned k_lane = (unsigned)(k0 + wn * EPW);
   const bool f_add = a.epi & CV_EPI_ADD, f_act = a.epi & CV_EPI_ACT, f_dact = a.epi & CV_EPI_DACT;
   const bool f_addg = a.epi & CV_EPI_ADD_GRID;
 #pragma unroll
@@ -308,14 +332,14 @@ __global__ __launch_bounds__(CV_THREADS, CV_MINWAVES) void k_conv_f32(ConvArgs a
       const int th = p / TW, tw = p % TW;
       const int oh = (ho0 + th) * G::OSH + G::OPH, ow = (wo0 + tw) * G::OSW + G::OPW;
       if (ho0 + th >= a.Ho || wo0 + tw >= a.Wo || oh >= a.Hout || ow >= a.Wout) continue;      // surplus pixel of an overhanging tile
-      const size_t o = (out_n + (size_t)oh * a.Wout + ow) * a.K + k0 + wn * EPW + c4 * 4;
+      const unsigned o = (out_n + (unsigned)(oh * a.Wout + ow)) * (unsigned)a.K + k_lane + c4 * 4;
       float4 v = *reinterpret_cast<const float4*>(ep + row * ES + c4 * 4);
       if (a.seam && (ow == 0 || ow == a.Wout - 1)) {      // odd image width: the two terms that cross the seam (k_dgrad_oddw_seam)
-        const float4 t = *reinterpret_cast<const float4*>(a.seam + (((size_t)n * a.Hout + oh) * 2 + (ow != 0)) * a.K + k0 + wn * EPW + c4 * 4);
+        const float4 t = *reinterpret_cast<const float4*>(a.seam + ((unsigned)((n * a.Hout + oh) * 2 + (ow != 0)) * (unsigned)a.K + k_lane + c4 * 4));
         v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
       }
       if (f_addg) {        // an addend that lives on the dense (sub-sampled) grid: the down-sampling branch's gradient
-        const float4 t = *reinterpret_cast<const float4*>(a.add + (grid_n + (size_t)(ho0 + th) * a.Wo + (wo0 + tw)) * a.K + k0 + wn * EPW + c4 * 4);
+        const float4 t = *reinterpret_cast<const float4*>(a.add + ((grid_n + (unsigned)((ho0 + th) * a.Wo + (wo0 + tw))) * (unsigned)a.K + k_lane + c4 * 4));
         v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
       }
       if (f_add) {
@@ -400,44 +424,71 @@ __device__ __forceinline__ void wgrad_f32_body(const float* __restrict__ x, cons
 
   f32x4 x_r[NX_IT], g_r[NG_IT];
   // Round 6: a vector instruction next to an fp32 MFMA costs matrix time (wino.hip), and this loader spent 277 of them per
-  // chunk of 72 MFMAs -- a modulo by the run-time width and 64-bit address arithmetic for every staged item.  Per item two registers now
-  // hold what does not change from chunk to chunk (its element offset inside the chunk's window and its (row, column) there); a chunk
-  // adds a scalar base, wraps the column with two compares (the window is at most one image width wide: checked once, else the generic
-  // path below) and zeroes rows outside the image: ~12 instructions per item, 32-bit offsets next to a scalar 64-bit base.
-  // (FAST: the launcher checked RW <= W and 32-bit element offsets per sample)
+  // chunk of 72 MFMAs -- a modulo by the run-time width and 64-bit address arithmetic for every staged item -- and then 120: two registers
+  // per item, a scalar base, two compares for the wrap and a select for the zero rows.  Now the items are fetched through buffer
+  // descriptors built per chunk from scalars (cv_rsrc above); per item ONE register holds its byte offset inside the chunk's window,
+  // computed once per workgroup, and the chunk's position (image, row, first column) advances in scalar registers without a division:
+  //  - g: the descriptor spans the chunk's pixels that exist, so the surplus pixels behind a row's end read zeros by the range check;
+  //  - x, a window inside the image's columns and not above it (all but the first chunk of a row and the first row, for the network's
+  //    shapes): the descriptor starts at the window's origin and ends with the image -- rows below the image are out of range (zeros);
+  //  - x, any other window (a wave-uniform branch): the descriptor spans the image.  A window that begins left of column 0 is taken
+  //    to begin at the wrapped column (a scalar), so an item's column wraps at most once, to the left by one image width (the window is
+  //    at most one image width wide: checked once, else the generic path below): compare, select, add.  A row below the image lies
+  //    behind the descriptor's end; a row above it has a negative offset, which as an unsigned number lies behind it as well.
+  // (FAST: the launcher checked RW <= W and that an image of x with two more rows, and an image of g, are below 2^30 elements)
+  // The generic body (!FAST) keeps its modulo, clamped load and selects on purpose: it serves windows wider than the image (columns
+  // wrap more than once, which the single scalar wrap above cannot express) and images beyond 32-bit byte offsets (which one descriptor
+  // cannot span).  No layer of the network reaches it (wgrad_fast), so its instruction count costs the step nothing.
   constexpr bool fast = FAST;
-  int x_rel[FAST ? NX_IT : 1], x_rc[FAST ? NX_IT : 1];
+  unsigned x_rel[FAST ? NX_IT : 1], g_rel[FAST ? NG_IT : 1];
+  int x_cl[FAST ? NX_IT : 1];
   if (FAST) {
     _Pragma("unroll") for (int it = 0; it < NX_IT; ++it) {
       WG_XITEM(it)
       (void)x_l_;
-      x_rel[it] = (x_row_ * W + x_col_) * C + x_c4_;
-      x_rc[it] = (x_row_ << 16) | x_col_;
+      x_rel[it] = (unsigned)((x_row_ * W + x_col_) * C + x_c4_) * 4u;
+      x_cl[it] = x_col_;
+    }
+    _Pragma("unroll") for (int it = 0; it < NG_IT; ++it) {
+      WG_GITEM(it)
+      g_rel[it] = (unsigned)(g_p_ * K + g_k4_) * 4u;
     }
   }
+  // position of the next chunk to fetch (FAST): image, output row, first output column
+  int nx_n = ch_begin / chunks_per_row / Ho, nx_ho = ch_begin / chunks_per_row % Ho, nx_wo0 = ch_begin % chunks_per_row * PK;
 #define WG_FETCH(CH)                                                                                                      \
   {                                                                                                                       \
-    const int row_ = (CH) / chunks_per_row, wo0_ = ((CH) % chunks_per_row) * PK;                                          \
-    const int n_ = row_ / Ho, ho_ = row_ % Ho;                                                                            \
     if (fast) {                                                                                                           \
-      const int h0_ = ho_ * SH - PAD, w0_ = wo0_ * SW - PAD, wc_ = W * C;                                                 \
-      const float* xs_ = x + (size_t)n_ * H * W * C + c0;                      /* scalar */                               \
-      const int base_ = (h0_ * W + w0_) * C;                                   /* scalar, may be negative */              \
-      _Pragma("unroll") for (int it = 0; it < NX_IT; ++it) {                                                              \
-        const int h = h0_ + (x_rc[FAST ? it : 0] >> 16), w = w0_ + (x_rc[FAST ? it : 0] & 0xffff);                        \
-        const bool in = (unsigned)h < (unsigned)H;                                                                        \
-        const int off = base_ + x_rel[FAST ? it : 0] + (w < 0 ? wc_ : 0) - (w >= W ? wc_ : 0);                            \
-        const f32x4 v = *reinterpret_cast<const f32x4*>(xs_ + (unsigned)(in ? off : 0));                                  \
-        x_r[it] = in ? v : (f32x4){0.f, 0.f, 0.f, 0.f};                                                                   \
+      const int n_ = nx_n, ho_ = nx_ho, wo0_ = nx_wo0;                                                                    \
+      nx_wo0 += PK;                                                                                                       \
+      if (nx_wo0 >= Wo) {                                                                                                 \
+        nx_wo0 = 0;                                                                                                       \
+        if (++nx_ho == Ho) { nx_ho = 0; ++nx_n; }                                                                         \
+      }                                                                                                                   \
+      const int h0_ = ho_ * SH - PAD, w0_ = wo0_ * SW - PAD;                                                              \
+      const float* xi_ = x + (size_t)n_ * H * W * C + c0;                      /* scalar: the image, this tile's channels */ \
+      const unsigned img_ = (unsigned)(H * W * C - c0) * 4u;                                                              \
+      const int base_ = (h0_ * W + w0_) * C;                                   /* scalar, negative above / left of the image */ \
+      if (h0_ >= 0 && w0_ >= 0 && w0_ + RW <= W) {                                                                        \
+        const __amdgpu_buffer_rsrc_t rs_ = cv_rsrc(xi_ + base_, img_ - (unsigned)base_ * 4u);                             \
+        _Pragma("unroll") for (int it = 0; it < NX_IT; ++it) x_r[it] = cv_ld16(rs_, x_rel[FAST ? it : 0], 0u);            \
+      } else {                                                                                                            \
+        const __amdgpu_buffer_rsrc_t rs_ = cv_rsrc(xi_, img_);                                                            \
+        const int ws_ = w0_ < 0 ? w0_ + W : w0_, hi_ = W - ws_;           /* columns hi_ and beyond of the window wrap */   \
+        const unsigned b4_ = (unsigned)((h0_ * W + ws_) * C) * 4u, wc_ = (unsigned)(W * C) * 4u;                          \
+        _Pragma("unroll") for (int it = 0; it < NX_IT; ++it) {                                                            \
+          const unsigned off = b4_ + x_rel[FAST ? it : 0] + (x_cl[FAST ? it : 0] >= hi_ ? 0u - wc_ : 0u);                 \
+          /* (row -1: at most -16, kept 32 bytes clear of the wrap of a 32-bit end address) */                            \
+          x_r[it] = cv_ld16(rs_, min(off, 0xffffffe0u), 0u);                                                              \
+        }                                                                                                                 \
       }                                                                                                                   \
       const float* gs_ = g + ((size_t)(n_ * Ho + ho_) * Wo + wo0_) * K + k0;   /* scalar */                               \
-      _Pragma("unroll") for (int it = 0; it < NG_IT; ++it) {                                                              \
-        WG_GITEM(it)                                                                                                      \
-        const bool gin = wo0_ + g_p_ < Wo;                                                                                \
-        const f32x4 gv = *reinterpret_cast<const f32x4*>(gs_ + (unsigned)(gin ? g_p_ * K + g_k4_ : 0));                   \
-        g_r[it] = gin ? gv : (f32x4){0.f, 0.f, 0.f, 0.f};                                                                 \
-      }                                                                                                                   \
+      const int npx_ = min(PK, Wo - wo0_);                                                                                \
+      const __amdgpu_buffer_rsrc_t grs_ = cv_rsrc(gs_, (unsigned)((npx_ - 1) * K + BMK) * 4u);                            \
+      _Pragma("unroll") for (int it = 0; it < NG_IT; ++it) g_r[it] = cv_ld16(grs_, g_rel[FAST ? it : 0], 0u);             \
     } else {                                                                                                              \
+    const int row_ = (CH) / chunks_per_row, wo0_ = ((CH) % chunks_per_row) * PK;                                          \
+    const int n_ = row_ / Ho, ho_ = row_ % Ho;                                                                            \
     _Pragma("unroll") for (int it = 0; it < NX_IT; ++it) {                                                                \
       WG_XITEM(it)                                                                                                        \
       (void)x_l_;                                                                                                         \
@@ -536,10 +587,10 @@ __global__ __launch_bounds__(CV_THREADS, 2) void k_wgrad_f32(const float* __rest
                                                              int Ho, int Wo, int chunks_per_slab, int nslabs) {
   wgrad_f32_body<BMK, BNC, PK, SH, SW, KS, FAST>(x, g, part, N, H, W, C, K, Ho, Wo, chunks_per_slab, nslabs, blockIdx.x);
 }
-// FAST (the staged window is at most one image width wide, element offsets of a sample fit 31 bits): every layer of the network
+// FAST (the staged window is at most one image width wide, byte offsets of a sample and of the rows beside it fit 32 bits): every layer of the network
 template <int PK, int SW, int KS>
 static inline bool wgrad_fast(int H, int W, int C, int K, int Ho, int Wo) {
-  return (PK - 1) * SW + KS <= W && (size_t)H * W * C < ((size_t)1 << 30) && (size_t)Ho * Wo * K < ((size_t)1 << 30);
+  return (PK - 1) * SW + KS <= W && (size_t)(H + 2) * W * C < ((size_t)1 << 30) && (size_t)Ho * Wo * K < ((size_t)1 << 30);
 }
 
 // Several layers in one launch (dl_conv2d_wgrad_batch_nhwc_f32, see include/delora_hip.h): layer table in the kernel arguments,
@@ -703,6 +754,8 @@ static int dispatch_conv(const ConvArgs& a, hipStream_t st) {
     // 16); the stem (8 input channels) has no other choice
     if (a.C % CV_CK || a.C <= 256) return launch_conv_128<G, BT, 8>(a, st);
   }
+  // (the 1x1 layers keep 16-channel chunks: 32-channel chunks halve the trips between barrier pairs but cost waves per SIMD -- the
+  // strided tile stages the skipped pixels too -- and a build with them measured slower forward: profiles/direct_addr_harness.txt)
   return launch_conv_128<G, BT, CV_CK>(a, st);
 }
 
@@ -792,6 +845,8 @@ extern "C" int dl_conv2d_nhwc_f32(const float* x, const float* w, float* y, cons
     return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_conv2d_nhwc_f32: kernel size must be 1 or 3, strides 1 or 2 (got %d, %d, %d)", ksize, stride_h, stride_w);
   if ((size_t)N * H * W * C >= ((size_t)1 << 31) || (size_t)N * H * W * K >= ((size_t)1 << 31))
     return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_nhwc_f32: tensors beyond 2^31 elements are not supported (split the batch)");
+  if ((size_t)H * W * C >= ((size_t)1 << 29) || (size_t)K * C * ksize * ksize >= ((size_t)1 << 29))
+    return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_nhwc_f32: an image or the weights of 2 GiB and more are not supported");
   // output size of the reference's padded convolution (circular pad 1 on W, zero pad 1 on H, kernel 3; or kernel 1 unpadded):
   // floor((X - 1) / stride) + 1 = ceil(X / stride)
   const int Ho = (H + stride_h - 1) / stride_h, Wo = (W + stride_w - 1) / stride_w;
@@ -836,6 +891,8 @@ extern "C" int dl_conv2d_dgrad_strided_nhwc_f32(const float* g, const float* w, 
   const int Ho = (H + stride_h - 1) / stride_h, Wo = (W + stride_w - 1) / stride_w;      // the layer's output grid (= g)
   if ((size_t)N * H * W * C >= ((size_t)1 << 31) || (size_t)N * Ho * Wo * K >= ((size_t)1 << 31))
     return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_dgrad_strided_nhwc_f32: tensors beyond 2^31 elements are not supported");
+  if ((size_t)Ho * Wo * K >= ((size_t)1 << 29) || (size_t)K * C * ksize * ksize >= ((size_t)1 << 29))
+    return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_dgrad_strided_nhwc_f32: an image or the weights of 2 GiB and more are not supported");
   // in the kernel's terms: input = g (K channels, the reduction), output channels = C.  The stride phases of an image whose width is
   // odd do not close under the wrap-around: they read zeros beside the grid and k_dgrad_oddw_fix adds the two seam terms.
   const bool odd_w = stride_w == 2 && (W & 1) && ksize == 3 && !dense && W >= 3;
