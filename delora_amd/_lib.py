@@ -32,6 +32,8 @@ SIGNATURES = {
     "dl_last_error": (ctypes.c_char_p, []),
     "dl_project_workspace_bytes": (_sz, [_i32, _i32, _i32, _i64, _i32]),
     "dl_project": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dl_reproject_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dl_reproject": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _SP, _vp, _vp, _vp, _vp, _vp]),
     "dl_normals": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
     "dl_nn_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dl_nn_correspond": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _SP, _i32, _vp, _vp, _vp, _vp, _vp]),

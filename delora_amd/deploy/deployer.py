@@ -5,8 +5,11 @@ same constructor argument, same ``step(preprocessed_dicts, epoch_losses, log_ima
 the same loss bookkeeping -- including its accumulation order, which gives sample j of a batch the weight
 (B-j)/B in the back-propagated ``loss_pc`` (deployer.py:309-312,329) -- but the per-sample Python loops are
 replaced by batched HIP launches (deploy/step_geometry.py) and nothing synchronises with the host inside a step.
-Plotting / MLflow image logging (deployer.py:73-162) is outside the hot path and not provided.
+A logged step (``log_images_bool=True``) additionally fills the reference's six ``log_*`` images (deployer.py:61-66,73-89) through one
+re-projection launch of the backend (``step_images``); ``log_image`` draws them (utility/plotting.py).
 """
+import os
+
 import torch
 
 from .. import geometry
@@ -45,6 +48,13 @@ class Deployer(object):
         self.geo = geometry_backend if geometry_backend is not None else step_geometry.HipStepGeometry()
         self.lossTransformation = torch.nn.MSELoss()
         self.training_bool = False
+        # the six images of the logged figure (deployer.py:61-66): [1,3,H,W] each, log_img_2_transformed [1,4,H,W]
+        self.log_img_1 = []
+        self.log_img_2 = []
+        self.log_img_2_transformed = []
+        self.log_pointwise_loss = []
+        self.log_normals_target = []
+        self.log_normals_transformed_source = []
         # float16 autocast: the trunk's inter-layer gradients are STORED in fp16 and start at (head gradient) / (H*W/64) -- below
         # fp16's normal range (6e-5) for O(1e-2) loss gradients -- so the backward runs on a scaled loss (dynamic scale, skipped steps
         # on overflow: torch's GradScaler, which hands scale and overflow flag to the fused Adam kernel without a host sync).
@@ -165,6 +175,10 @@ class Deployer(object):
             groups.setdefault(self.img_projection.sensor(d["dataset"]).key(), []).append(i)
         flags = geometry.loss_flags(cfg)
         T_rows, term_rows, count_rows, vis_rows = [None] * B, [None] * B, [None] * B, [None] * B
+        # a logged step keeps (references to) what the figure is drawn from: the group of sample 0 and the group of the last sample
+        want_images = (bool(log_images_bool) and not cfg["inference_only"] and not cfg.get("po2po_alone", False)
+                       and hasattr(self.geo, "step_images"))
+        image_first = image_last = None
         for idx in groups.values():
             dataset = preprocessed_dicts[idx[0]]["dataset"]
             sensor = self.img_projection.sensor(dataset)
@@ -182,6 +196,10 @@ class Deployer(object):
                     term_rows[i] = terms_g[k]
                     count_rows[i] = counts_g[k] if counts_g is not None else None
                     vis_rows[i] = vis_g[k] if vis_g is not None else None
+                if want_images and i == 0:
+                    image_first = (prepared, k, T_g)
+                if want_images and i == B - 1:
+                    image_last = (prepared, k)
         single = len(groups) == 1
         computed_transformations = T_g if single else torch.stack(T_rows)
 
@@ -233,5 +251,56 @@ class Deployer(object):
                 keys.append("visible_pixels_epoch")
                 vals.append(visible[B - 1].detach())                      # last sample only (:349-352)
             self._accumulate(epoch_losses, keys, vals)
+        if want_images:
+            self._fill_log_images(image_first, image_last)
         self.last_step = {"loss_terms": terms.detach(), "pair_counts": counts, "losses": {k: v.detach() for k, v in losses.items()}}
         return epoch_losses, computed_transformations
+
+    # ------------------------------------------------------------------------------------------------ the logged figure
+    def _fill_log_images(self, first, last):
+        """The six images of a logged step.  log_img_1 / log_img_2 are the LAST sample's (the reference's loop variable survives the
+        loop, deployer.py:269-270), everything else is sample 0's (:316-322, :354-356).  The target normal map is the target's normal
+        image itself: re-projecting the kept points together with their normals (:75-77) reproduces it."""
+        with torch.no_grad():
+            prepared, k = last
+            self.log_img_1 = prepared["stacked"][k:k + 1, 0:3].detach().clone()
+            self.log_img_2 = prepared["stacked"][k:k + 1, 4:7].detach().clone()
+            prepared, k, T_g = first
+            moved4, paired9, _ = self.geo.step_images(T_g.detach(), prepared, k)
+            self.log_img_2_transformed = moved4
+            self.log_pointwise_loss = paired9[:, 6:9]
+            self.log_normals_transformed_source = paired9[:, 3:6]
+            self.log_normals_target = prepared["normals"][k:k + 1, 0].detach().clone()
+
+    def log_image(self, epoch, string):
+        """Draw the six images of the last logged step (deployer.py:91-100) into ``<image_log_dir or /tmp>/<run_name>_<epoch:05d><string>.png``,
+        log the file as an MLflow artifact when mlflow is importable, and return its path."""
+        from ..utility import plotting
+        path = os.path.join(self.config.get("image_log_dir") or "/tmp", self.config["run_name"] + "_" + format(epoch, "05d") + string + ".png")
+        plotting.plot_lidar_image(
+            input=[self.log_img_1, self.log_img_2, self.log_img_2_transformed, self.log_pointwise_loss, self.log_normals_target,
+                   self.log_normals_transformed_source],
+            label="target", iteration=(epoch + 1) * self.steps_per_epoch if self.training_bool else epoch, path=path,
+            training=self.training_bool)
+        try:
+            import mlflow
+        except ImportError:
+            mlflow = None
+        if mlflow is not None:
+            mlflow.log_artifact(path)
+        return path
+
+    def image_logging_enabled(self):
+        """Image logging is on iff visualize_images is set, po2po_alone is not, and the figure has somewhere to go: an
+        ``image_log_dir`` in the config or an importable mlflow."""
+        if not self.config.get("visualize_images", False) or self.config.get("po2po_alone", False):
+            return False
+        if not hasattr(self.geo, "step_images"):            # (a geometry backend without the re-projection fills no images)
+            return False
+        if "image_log_dir" in self.config:
+            return True
+        try:
+            import mlflow  # noqa: F401
+        except ImportError:
+            return False
+        return True

@@ -95,4 +95,12 @@ class HipStepGeometry:
         nn, visible, match = geometry.nn_correspond(src, src_n, tgt_pk, tgt_n_pk, T, sensor,
                                                     need_without_normals=need_without_normals)
         terms, counts = geometry.icp_loss(T, src, src_n, match, nn, flags)
+        prepared["nn"], prepared["match"], prepared["T"] = nn, match, T          # what a logged step's images need: references only
         return terms, counts, visible
+
+    def step_images(self, T, prepared, sample):
+        """The re-projected images of one sample of a logged step: ONE dl_reproject call with B = 1 on that sample's views.
+        Returns (moved4 [1,4,H,W], paired9 [1,9,H,W], src_pix [1,2,H,W] int32) on the device."""
+        s = slice(sample, sample + 1)
+        return geometry.reproject(prepared["images"][s, 1], T[s], prepared["sensor"], src_normals=prepared["normals"][s, 1],
+                                  match=prepared["match"][s], nn_pix=prepared["nn"][s])

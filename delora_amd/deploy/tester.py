@@ -1,7 +1,8 @@
 """``Tester``: run a trained model over the test sequences and integrate the predicted transforms into trajectories.
-Mirror of src/deploy/tester.py:16-162 without MLflow/plot artefacts: per sequence it writes the KITTI-format pose file,
+Mirror of src/deploy/tester.py:16-162 without the trajectory plots: per sequence it writes the KITTI-format pose file,
 the raw transformations and the integrated poses (the same three files the reference logs, deployer.py:96-117), into
-``config["output_dir"]`` (default /tmp, as the reference)."""
+``config["output_dir"]`` (default /tmp, as the reference).  With image logging on (Deployer.image_logging_enabled) every tenth step
+fills the six logged images and writes the figure (tester.py:61-64,95-98)."""
 import os
 
 import numpy as np
@@ -48,10 +49,14 @@ class Tester(deployer.Deployer):
         epoch_losses = {k: 0.0 for k in ("loss_epoch", "loss_point_cloud_epoch", "loss_field_of_view_epoch", "loss_po2po_epoch",
                                          "loss_po2pl_epoch", "loss_pl2pl_epoch", "visible_pixels_epoch")}
         cur_ds, cur_seq, dataset = 0, 0, self.config["datasets"][0]
+        log_images = not self.config["inference_only"] and self.image_logging_enabled()
         for index, preprocessed_dicts in enumerate(feed.DevicePrefetcher(dataloader, self.device)):
             with torch.set_grad_enabled(False):
                 if not self.config["inference_only"]:
-                    epoch_losses, T = self.step(preprocessed_dicts=preprocessed_dicts, epoch_losses=epoch_losses)
+                    log_now = log_images and not index % 10              # every tenth index (tester.py:61-64 of the reference)
+                    epoch_losses, T = self.step(preprocessed_dicts=preprocessed_dicts, epoch_losses=epoch_losses, log_images_bool=log_now)
+                    if log_now:
+                        self.log_image(epoch=index, string="_" + preprocessed_dicts[0]["dataset"])
                 else:
                     T = self.step(preprocessed_dicts=preprocessed_dicts, epoch_losses=epoch_losses)
             for d in preprocessed_dicts:

@@ -165,22 +165,35 @@ class Trainer(deployer.Deployer):
             self._graphed.take_epoch_sums()             # (steps replayed outside an epoch, e.g. by a caller's own loop)
             if self._graphed_phase != bool(self.config["unsupervised_at_start"]):
                 self._graphed = None                    # the training phase changed: the old capture (and its memory pool) goes now
+        # the logged figure (trainer.py:70-80 of the reference): the first and the last step of an epoch fill the six images, on the
+        # process of rank 0 only.  A logged step always runs eagerly -- it is neither replayed, nor counted in graph_steps, nor timed
+        # by the `auto` probe -- so that a captured step never contains the re-projection.
+        log_images = self.rank == 0 and self.image_logging_enabled()
+        last_step = len(dataloader) - 1 if log_images else -1
         for counter, preprocessed_dicts in enumerate(iterator):
             phase = bool(self.config["unsupervised_at_start"])
             mode = "eager" if policy == "off" else ("graph" if policy == "on" else self._graph_decision.get(phase, "probe"))
-            if mode == "graph":
+            log_now = log_images and (counter == 0 or counter == last_step)
+            if mode == "graph" and not log_now:
                 epoch_losses = self._graphed_step(preprocessed_dicts, epoch_losses)
                 continue
 
-            def run_eager(batch=preprocessed_dicts, ep=epoch_losses):
+            def run_eager(batch=preprocessed_dicts, ep=epoch_losses, log=log_now):
                 self.optimizer.zero_grad(set_to_none=True)
-                return self.step(preprocessed_dicts=batch, epoch_losses=ep, log_images_bool=False)[0]
-            epoch_losses = self._probe_step(phase, run_eager) if mode == "probe" else run_eager()
+                return self.step(preprocessed_dicts=batch, epoch_losses=ep, log_images_bool=log)[0]
+            epoch_losses = self._probe_step(phase, run_eager) if (mode == "probe" and not log_now) else run_eager()
+            if log_now and epoch == 0 and counter == 0:
+                # the network's initial state (trainer.py:77-80)
+                self.log_image(epoch=epoch, string="_start_" + self._batch_dataset(preprocessed_dicts))
             if show and counter % every == 0:          # one host sync per `every` steps instead of one per step
                 iterator.set_infos({"loss": f'{float(epoch_losses["loss_epoch"]) / (counter + 1):.6f}',
                                     "loss_po2pl": f'{float(epoch_losses["loss_po2pl_epoch"]) / (counter + 1):.6f}',
                                     "loss_pl2pl": f'{float(epoch_losses["loss_pl2pl_epoch"]) / (counter + 1):.6f}'})
         return self._fold_graph_sums(epoch_losses)
+
+    @staticmethod
+    def _batch_dataset(batch):
+        return batch.dataset if hasattr(batch, "dataset") else batch[0]["dataset"]
 
     def _graphed_step(self, preprocessed_dicts, epoch_losses):
         """The step replayed as one captured HIP graph (deploy/graph_step.py; ragged batches go through static buffers of
@@ -359,6 +372,8 @@ class Trainer(deployer.Deployer):
                     if keep > 0 and not epoch % keep:
                         self.save_checkpoint(os.path.join(out_dir, self.config["training_run_name"] + "_checkpoint_epoch_" + str(epoch) + ".pth"),
                                              epoch, metrics["loss_epoch"])
+                    if self.image_logging_enabled():
+                        self.log_image(epoch=epoch, string="_image")      # the last step's images (trainer.py:179-180)
                 # identity pre-training ends once its loss is small (trainer.py:184-186); all ranks see the same reduced value
                 if not self.config["unsupervised_at_start"] and metrics["loss_epoch"] < 1e-2:
                     self.config["unsupervised_at_start"] = True

@@ -153,6 +153,34 @@ def nn_correspond(src_image4, src_normals, tgt_packed, tgt_normals_packed, T, se
     return nn, vis, match
 
 
+def reproject(src_image4, T, sensor, src_normals=None, match=None, nn_pix=None, want_paired=True, want_src_pix=True):
+    """Range images of the TRANSFORMED source image (dl_reproject): the pictures of a logged step.  ``src_image4 [B,>=3,H,W]``
+    planar, ``T [B,4,4]``; ``src_normals [B,3,H,W]``, ``match [B,6,H,W]`` and ``nn_pix [B,H,W]`` (from nn_correspond) are given
+    together or not at all.  Returns (moved4 [B,4,H,W], paired9 [B,9,H,W]|None, src_pix [B,2,H,W] int32|None)."""
+    lib = _lib.load()
+    _require_cuda(src_image4, T, src_normals, match, nn_pix)
+    s, s_ss = _planar(src_image4, 3)
+    given = [t is not None for t in (src_normals, match, nn_pix)]
+    if any(given) and not all(given):
+        raise ValueError("src_normals, match and nn_pix are given together or not at all")
+    n, n_ss = _planar(src_normals, 3) if given[0] else (None, 0)
+    mt, mt_ss = _planar(match, 6) if given[1] else (None, 0)
+    if given[2] and (nn_pix.dtype != torch.int32 or not nn_pix.is_contiguous()):
+        raise ValueError("nn_pix must be a contiguous int32 [B,H,W] tensor")
+    B, H, W, dev = s.shape[0], sensor.H, sensor.W, s.device
+    if tuple(s.shape[2:]) != (H, W):
+        raise ValueError(f"the image is {tuple(s.shape[2:])}, the sensor {(H, W)}")
+    Tc = T.detach().contiguous().float()
+    moved4 = torch.empty((B, 4, H, W), dtype=torch.float32, device=dev)
+    paired9 = torch.empty((B, 9, H, W), dtype=torch.float32, device=dev) if (want_paired and all(given)) else None
+    src_pix = torch.empty((B, 2, H, W), dtype=torch.int32, device=dev) if want_src_pix else None
+    ws = torch.empty((lib.dl_reproject_workspace_bytes(B, H, W) // 8,), dtype=torch.int64, device=dev)
+    _lib.check(lib.dl_reproject(_ptr(s), s_ss, _ptr(n), n_ss, _ptr(mt), mt_ss, _ptr(nn_pix), _ptr(Tc), B,
+                                ctypes.byref(sensor.struct), _ptr(moved4), _ptr(paired9), _ptr(src_pix), _ptr(ws), _stream()),
+               "dl_reproject")
+    return moved4, paired9, src_pix
+
+
 # bench.py sets this to a callable returning a fresh timer handle (LossTimers.new): the streaming loss kernel of every
 # training step is then launched with its own begin/end timestamps attached, so that its duration can be measured
 # inside real steps (dl_icp_loss_partial_timed)

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
+#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
 
 typedef void* dl_stream;
 
@@ -158,6 +158,50 @@ int dl_nn_correspond(const float* src_image4, int64_t src_ss, const float* src_n
                      const float* tgt_packed, int64_t tgt_ss, const float* tgt_normals_packed, int64_t tgtn_ss,
                      const float* T, int32_t B, const dl_sensor* sensor, int32_t need_without_normals,
                      int32_t* nn_pix, float* match, int32_t* visible, void* workspace, dl_stream stream);
+
+/* Bytes of scratch dl_reproject needs: exactly the two uint64 key planes [B][2][H*W], rounded up to 16 bytes; 0 for a
+ * non-positive size. */
+size_t dl_reproject_workspace_bytes(int32_t B, int32_t H, int32_t W);
+
+/*
+ * Re-projection of the TRANSFORMED source image: the range images of the logged step figure.
+ * Replaces, for Deployer.log_image (src/deploy/deployer.py:73-100), the host-side pair lists and the three project_to_img calls
+ * of a logged step (deployer.py:80-89, :317-320; src/losses/icp_losses.py:196-206): a vote pass over the source pixels (up to two
+ * 64-bit atomicMin per occupied pixel) and a resolve pass over the output pixels that recomputes the winner's values from its
+ * source pixel.  The inputs are the tensors of dl_icp_loss_fwd:
+ *   src_image4 [B][4][H][W] planar source image (scan stride src_ss elements, >= 3*H*W; planes 0..2 are read)
+ *   src_normals [B][3][H][W] source normals (scan stride srcn_ss >= 3*H*W)
+ *   match      [B][6][H][W] from dl_nn_correspond (scan stride match_ss >= 6*H*W)
+ *   nn_pix     [B][H][W]   its map; only the sign is used
+ *   T          [B][4][4]   fp32 row-major source->target transforms
+ *   moved4     [B][4][H][W] out: x', y', z', range' of the winning transformed source point, the winner taken over ALL occupied
+ *                          source pixels (the reference's image_2_transformed, deployer.py:317-320)
+ *   paired9    [B][9][H][W] out (may be NULL): the winner taken over the PAIRS WITH NORMALS only; planes 0..2 the transformed
+ *                          point, 3..5 the rotated source normal R n, 6..8 the residual vector d = s' - m (m = match planes 0..2)
+ *                          (image_2_transformed_and_normals_and_pointwise_loss, channels 0..8: deployer.py:80-89)
+ *   src_pix    [B][2][H][W] int32 out (may be NULL): the source pixel index of the winner of moved4 (plane 0) and of paired9
+ *                          (plane 1), -1 where there is none
+ *   workspace  dl_reproject_workspace_bytes(B, H, W) bytes, 16-byte aligned
+ * src_normals, match and nn_pix may be NULL only together; paired9 must then be NULL as well.  When paired9 is NULL, plane 1 of
+ * src_pix is still written, all -1.  Every element of every output is written on every call; empty pixels hold +0.0 (-1 in src_pix).
+ * The contract, bit for bit (tests/reproject_ref.py is its plain restatement; it builds on dl_project's):
+ *   a source pixel is occupied iff !(x == 0 && y == 0 && z == 0) (the rule of dl_nn_correspond);
+ *   the transformed point is q = fma(m2, z, fma(m1, y, m0 * x)) + m3 per row of T (the operations of dl_icp_loss_fwd), the rotated
+ *     normal the same chain without the addition, d = q - m, all in fp32;
+ *   range, u, v, half-to-even rounding and the inside test of q are dl_project's: a NaN coordinate is outside, an infinite range
+ *     still votes and loses to every finite one;
+ *   the winner of a pixel is the smallest (uint32 bit pattern of range', source pixel index);
+ *   a source pixel is PAIRED iff it is occupied, nn_pix >= 0, its source normal is not the zero vector and the normal in match
+ *     planes 3..5 is not the zero vector (the pair set of icp_losses.py:48-52,110-121);
+ *   a non-finite T[b] stays in sample b: every other sample's output is the same to the bit.
+ * DL_ERR_INVALID_ARGUMENT before any launch: a null src_image4 / T / sensor / moved4 / workspace; B <= 0, H < 2 or W < 2;
+ * 2*B*H*W beyond 2^31 - 1; the pair inputs given in part; paired9 without them; a scan stride below the dense size; a workspace
+ * that is not 16-byte aligned.  The call is three kernels on `stream` (key fill, vote, resolve): no synchronisation, allocation,
+ * read-back or floating-point atomic, capturable into a HIP graph.
+ */
+int dl_reproject(const float* src_image4, int64_t src_ss, const float* src_normals, int64_t srcn_ss, const float* match,
+                 int64_t match_ss, const int32_t* nn_pix, const float* T, int32_t B, const dl_sensor* sensor, float* moved4,
+                 float* paired9, int32_t* src_pix, void* workspace, dl_stream stream);
 
 /* Bytes of scratch dl_icp_loss_fwd needs (per-block partial sums). */
 size_t dl_icp_loss_workspace_bytes(int32_t B, int32_t H, int32_t W);
