@@ -47,6 +47,29 @@ class OdometryModel(torch.nn.Module):
             self.fully_connected_translation = _mlp(act, [n_feat, 100, 3])
         self.geometry_handler = model_parts.GeometryHandler(config=config)
 
+    def _tower_weights(self):
+        return [m.weight for m in self.feature_extractor if isinstance(m, torch.nn.Conv2d)]
+
+    def forward_tower(self, stacked):
+        """``pre_feature_extraction`` on the HIP path: the planar pair ``[B,8,H,W]`` through ``ring_conv.RingTower`` (five narrow MFMA
+        layers per image, both images per launch), ``RingStemWide``, the trunk and the fused heads.  Returns None when that path does
+        not take the input (``ResNetModified.wide_path_dtype``: CPU tensors, narrow networks, widths not divisible by 4, active
+        dropout, ``cnn_impl: modules``); ``cnn_impl: hip`` makes that an error."""
+        dtype = self.resnet.wide_path_dtype(stacked)
+        if dtype is None:
+            if self.config.get("cnn_impl", "auto") == "hip" and stacked.is_cuda:
+                raise RuntimeError(f"cnn_impl 'hip': the HIP feature tower does not support input {tuple(stacked.shape)} / dtype {stacked.dtype}"
+                                   + (" with active dropout" if self.resnet.dropout_active() else ""))
+            return None                      # (the resnet prints the one module-path note for its 80-channel input)
+        pooled, _ = self.resnet.pooled_features_wide(stacked, self._tower_weights(), dtype)
+        with torch.autocast("cuda", enabled=False):
+            if self._fused_heads_ok(stacked):
+                act = 2 if self.config["activation_fct"] == "relu" else 1
+                fr, ft = self.fully_connected_rotation, self.fully_connected_translation
+                return model_parts.FusedHeads.apply(pooled.float(), act, self.resnet.fc.weight, self.resnet.fc.bias, fr[1].weight, fr[1].bias,
+                                                    fr[3].weight, fr[3].bias, ft[1].weight, ft[1].bias, ft[3].weight, ft[3].bias)
+            return self._heads(self.resnet.fc(pooled))
+
     def forward_features(self, image_1, image_2):
         if self.pre_feature_extraction:
             x = torch.cat((self.feature_extractor(image_1), self.feature_extractor(image_2)), dim=1)
@@ -91,10 +114,19 @@ class OdometryModel(torch.nn.Module):
 
     def forward(self, image_1, image_2=None):
         """``forward(image_1, image_2)`` as the reference; ``forward(stacked)`` with a ``[B,8,H,W]`` tensor skips the
-        concatenation copy (only without the per-image feature tower)."""
+        concatenation copy.  With the per-image feature tower both forms take ``forward_tower`` when the HIP path takes the input
+        (the gate is decided on the shapes before anything is copied), else the tower's modules on the two images."""
         if image_2 is None:
             if self.pre_feature_extraction:
+                out = self.forward_tower(image_1)
+                if out is not None:
+                    return out
                 image_1, image_2 = image_1[:, :4], image_1[:, 4:]
             else:
                 return self.forward_stacked(image_1)
+        elif self.pre_feature_extraction and (self.resnet.wide_path_dtype(image_1, pair=True) is not None
+                                              or (image_1.is_cuda and self.config.get("cnn_impl", "auto") == "hip")):
+            out = self.forward_tower(torch.cat((image_1, image_2), dim=1))          # (two 4-channel images: the only copy)
+            if out is not None:
+                return out
         return self._heads(self.forward_features(image_1=image_1, image_2=image_2)[-1])

@@ -120,28 +120,34 @@ class ResNetModified(torch.nn.Module):
             w.data = w.data.contiguous(memory_format=torch.channels_last)
         return self
 
-    def _note_module_path(self, x):
+    def _note_module_path(self, x, why=None):
         """One line per (shape, dtype, mode) whenever a CUDA input takes the module path (library convolutions + ring ops) instead of
-        the HIP stem + trunk: a 5x slower path must not be taken silently (narrow test networks, widths not divisible by 4)."""
+        the HIP stem + trunk: a 5x slower path must not be taken silently (narrow test networks, widths not divisible by 4).
+        ``why``: the caller's own reason (the feature tower in front of this network, models/model.py)."""
         if not x.is_cuda or self.impl == "modules":
             return
         key = (tuple(x.shape), x.dtype, torch.is_autocast_enabled(), self.training and self.use_dropout)
         seen = self.__dict__.setdefault("_module_path_noted", set())
         if key not in seen:
             seen.add(key)
-            why = ("autocast shapes do not tile (csrc/convh.hip)" if key[2]
-                   else "channel counts are not multiples of 64, or the width is not a multiple of 4"
-                   + (" (active dropout needs the HIP stem as well as the trunk)" if key[3] else ""))
+            why = why or ("autocast shapes do not tile (csrc/convh.hip)" if key[2]
+                          else "channel counts are not multiples of 64, or the width is not a multiple of 4"
+                          + (" (active dropout needs the HIP stem as well as the trunk)" if key[3] else ""))
             print(f"[delora_amd] CNN input {key[0]} {str(x.dtype).replace('torch.', '')} runs on the MODULE path (library convolutions), "
                   f"not on the HIP stem + trunk: {why}", flush=True)
 
-    def hip_path_takes(self, H, W, in_channels=8, batch=1):
-        """Whether an ``[N,in_channels,H,W]`` fp32 CUDA input would run on the channels-last HIP stem + trunk (shape test
-        only: ``ring_conv.supported`` / ``stem_supported``: full-width channel counts, a width divisible by 4).  True for BASELINE's
+    def hip_path_takes(self, H, W, in_channels=None, batch=1):
+        """Whether an ``[N,in_channels,H,W]`` fp32 CUDA input (default: this network's own input channels -- 8, or the feature
+        tower's 80) would run on the channels-last HIP stem + trunk (shape test only: ``ring_conv.supported`` / ``stem_supported``:
+        full-width channel counts, a width divisible by 4).  True for BASELINE's
         images and for the reference's shipped 64 x 720 and 64 x 512 (tiles hang over the edges of maps that do not divide)."""
         if self.impl == "modules" or W % 4:
             return False
         C0 = self.conv1.out_channels
+        if in_channels is None:
+            in_channels = self.conv1.in_channels
+        if in_channels == ring_conv.TOWER_CHANNELS and not ring_conv.tower_supported((batch, 8, H, W)):
+            return False
         return (ring_conv.stem_supported((batch, in_channels, H, W), C0)
                 and ring_conv.supported((batch, H, W // 4, C0), self._trunk_blocks()[0]))
 
@@ -159,7 +165,7 @@ class ResNetModified(torch.nn.Module):
         dtype = torch.get_autocast_dtype("cuda")
         N, Cin, Hin, Win = x.shape
         C0 = self.conv1.out_channels
-        if dtype not in ring_conv.DTYPE_CODE or Win % 4 or not ring_conv.stem_supported((N, Cin, Hin, Win), C0):
+        if dtype not in ring_conv.DTYPE_CODE or Win % 4 or not ring_conv.planar_stem_supported((N, Cin, Hin, Win), C0):
             return None
         return dtype if ring_conv.supported_h((N, Hin, Win // 4, C0), self._trunk_blocks()[0]) else None
 
@@ -205,7 +211,7 @@ class ResNetModified(torch.nn.Module):
                 feat = ring_conv.RingTrunkH.apply(x0, ring_conv.ACT[act], blocks, half, *weights)     # [N,C'] fp32
             return feat, None, None
         if (self.hip_trunk_applicable((N, Hin, Win // 4, C0), x) and Win % 4 == 0
-                and ring_conv.stem_supported(tuple(x.shape), C0)):
+                and ring_conv.planar_stem_supported(tuple(x.shape), C0)):
             # channels-last from the first layer on: stem (conv1 + act + pool) and layer1..layer4 on the HIP kernels
             blocks, weights = self._trunk_blocks()
             if self.dropout_active():
@@ -217,6 +223,40 @@ class ResNetModified(torch.nn.Module):
             x4 = ring_conv.RingTrunk.apply(x0, ring_conv.ACT[act], blocks, *weights)          # [N,H',W',C']
             return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), None
         return None, None, None
+
+    def wide_path_dtype(self, stacked, pair=False):
+        """Whether the planar image pair ``[B,8,H,W]`` of a network behind the feature tower runs on the HIP tower + wide stem + trunk:
+        an fp32 CUDA tensor, a full-width network with 80 input channels, a width divisible by 4, no active dropout.  Returns None
+        (no), torch.float32, or -- inside ``torch.autocast`` -- the half-precision dtype the trunk then runs in.  ``pair``: ``stacked``
+        is the first ``[B,4,H,W]`` image of a pair that has not been concatenated yet (a shape test before the copy)."""
+        if (self.impl == "modules" or not stacked.is_cuda or stacked.dtype != torch.float32 or self.dropout_active()
+                or self.conv1.in_channels != ring_conv.TOWER_CHANNELS or stacked.dim() != 4):
+            return None
+        B, C, H, W = stacked.shape
+        if pair:
+            C *= 2
+        C0 = self.conv1.out_channels
+        if W % 4 or not ring_conv.tower_supported((B, C, H, W)) or not ring_conv.stem_supported((B, ring_conv.TOWER_CHANNELS, H, W), C0):
+            return None
+        blocks = self._trunk_blocks()[0]
+        if torch.is_autocast_enabled():
+            dtype = torch.get_autocast_dtype("cuda")
+            return dtype if dtype in ring_conv.DTYPE_CODE and ring_conv.supported_h((B, H, W // 4, C0), blocks) else None
+        return torch.float32 if ring_conv.supported((B, H, W // 4, C0), blocks) else None
+
+    def pooled_features_wide(self, stacked, tower_weights, dtype):
+        """The globally pooled feature ``[B,C']`` (fp32) of an image pair behind the feature tower, all on HIP kernels: ``RingTower``
+        and ``RingStemWide`` in fp32 (inside autocast too, as the 8-channel stem), then the trunk in ``dtype`` (``wide_path_dtype``).
+        Returns (feat, last feature map as NCHW view or None)."""
+        act = ring_conv.ACT["relu" if self.activation_fct == "relu" else "tanh"]
+        blocks, weights = self._trunk_blocks()
+        with torch.autocast("cuda", enabled=False):
+            xw = ring_conv.RingTower.apply(stacked, act, False, *tower_weights)            # [B,H,W,128], channels 80.. zero
+            x0 = ring_conv.RingStemWide.apply(xw, self.conv1.weight, act, True)             # [B,H,W/4,C0]
+            if dtype != torch.float32:
+                return ring_conv.RingTrunkH.apply(x0, act, blocks, dtype, *weights), None
+            x4 = ring_conv.RingTrunk.apply(x0, act, blocks, *weights)
+            return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2)
 
     def forward(self, x):
         act = "relu" if self.activation_fct == "relu" else "tanh"
@@ -236,6 +276,9 @@ class ResNetModified(torch.nn.Module):
         if not self.dropout_active() and self.hip_trunk_applicable((N, H0, Wp - 2, C0), p):
             # channels-last trunk: layer1..layer4 as one autograd Function on the fp32 matrix cores
             blocks, weights = self._trunk_blocks()
+            if Cin == ring_conv.TOWER_CHANNELS:        # behind the feature tower: tower and stem ran as library convolutions
+                self._note_module_path(x, why="the feature tower and the stem run as library convolutions (a width that is not a multiple "
+                                       "of 4, or an input the HIP tower does not take); layer1..layer4 run on the HIP trunk")
             x0 = p[..., 1:-1].permute(0, 2, 3, 1).contiguous()
             x4 = ring_conv.RingTrunk.apply(x0, ring_conv.ACT[act], blocks, *weights)          # [N,H',W',C']
             out = self.fc(ring_conv.MeanHW.apply(x4))

@@ -426,10 +426,20 @@ def channel_scale(x, scale):
     return y
 
 
+TOWER_CHANNELS = 80          # stem input behind the per-image feature tower: 2 x 40 channels
+TOWER_PITCH = 128            # ... held in a [N,H,W,128] buffer whose channels 80..127 are zero (``RingStemWide``)
+
+
 def stem_supported(x_shape, out_channels):
-    """Whether RingStem takes an input ``[N,C,H,W]``: 8 input channels per chunk, 64-channel output tiles, a width that halves twice."""
+    """Whether the HIP stem takes an input ``[N,C,H,W]``: ``RingStem`` for 8 input channels per chunk, ``RingStemWide`` for the 80
+    channels of the feature tower; 64-channel output tiles, a width that halves twice."""
     N, C, H, W = x_shape
-    return C % 8 == 0 and C % 16 != 0 and out_channels % 64 == 0 and W % 4 == 0 and W >= 4 and H >= 1
+    return ((C % 8 == 0 and C % 16 != 0) or C == TOWER_CHANNELS) and out_channels % 64 == 0 and W % 4 == 0 and W >= 4 and H >= 1
+
+
+def planar_stem_supported(x_shape, out_channels):
+    """``stem_supported`` for the planar-input ``RingStem`` alone (its fused weight gradient is the 8-channel network's path)."""
+    return stem_supported(x_shape, out_channels) and x_shape[1] % 16 != 0
 
 
 class RingStem(torch.autograd.Function):
@@ -489,6 +499,150 @@ class RingStem(torch.autograd.Function):
             if seed:                                   # the input went through the dropout: the same mask, from the saved seed
                 gx = gx * dropout_scale(seed[0], SITE_INPUT, ctx.drop_p, x8.numel()).view(x8.shape).permute(0, 3, 1, 2)
         return ((gx if want_x else None), dw, None) + extra
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The per-image feature tower of ``pre_feature_extraction`` (reference src/models/model.py:30-54) on the narrow family
+# (csrc/tower.hip) and the 80-channel stem behind it.
+TOWER_PLAN = ((4, 8), (8, 16), (16, 24), (24, 32), (32, 40))         # (C, K) of the five layers
+
+
+def _view(pitch, offset=0, group=1):
+    """{pitch, offset, group} of include/delora_hip.h (narrow family): a dense ``[N,H,W,CH]`` tensor is ``_view(CH)``."""
+    return (ctypes.c_int32 * 3)(int(pitch), int(offset), int(group))
+
+
+def tower_conv(x, w, y, shape, x_view, y_view, act=0, epilogue=0, dsrc=None, dsrc_view=None, transposed=False):
+    """``y = epilogue(conv(x, w))`` of the narrow family into the caller's ``y``: ``shape`` = (N, H, W, C, K); w ``[K,3,3,C]``
+    (``transposed``: the forward weight ``[C,3,3,K]`` of the layer whose input gradient is taken); views as ``_view``."""
+    lib = _lib.load()
+    N, H, W, C, K = shape
+    _lib.check(lib.dl_tower_conv3x3_nhwc_f32(_ptr(x), _ptr(w), _ptr(y), _ptr(dsrc), N, H, W, C, K, x_view, y_view, dsrc_view, int(transposed),
+                                             int(act), int(epilogue), _stream()), "dl_tower_conv3x3_nhwc_f32")
+    return y
+
+
+def tower_wgrad(x, g, shape, x_view, g_view):
+    """``dW [K,3,3,C]`` of a narrow layer from its input x and output gradient g (views as ``_view``); fixed-order partial sums."""
+    lib = _lib.load()
+    N, H, W, C, K = shape
+    nbytes = lib.dl_tower_wgrad_workspace_bytes(N, H, W, C, K)
+    if not nbytes:
+        raise _lib.DeloraHipError(f"dl_tower_wgrad3x3_nhwc_f32 does not support N={N} H={H} W={W} C={C} K={K}")
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
+    dw = torch.empty((K, 3, 3, C), dtype=torch.float32, device=x.device)
+    _lib.check(lib.dl_tower_wgrad3x3_nhwc_f32(_ptr(x), _ptr(g), _ptr(dw), _ptr(ws), N, H, W, C, K, x_view, g_view, _stream()),
+               "dl_tower_wgrad3x3_nhwc_f32")
+    return dw
+
+
+def tower_supported(x_shape):
+    """Whether ``RingTower`` takes a planar input ``[B,8,H,W]``: two 4-channel images per sample, a wide stem input below 2^31
+    elements (the C side's 32-bit offsets)."""
+    B, C, H, W = x_shape
+    return C == 8 and B >= 1 and H >= 1 and W >= 1 and B * H * W * TOWER_PITCH < (1 << 31)
+
+
+class RingTower(torch.autograd.Function):
+    """The five 3x3 ring convolutions + activation in front of the pose CNN (reference src/models/model.py:30-54), for both images
+    of every sample at once: planar ``[B,8,H,W]`` (= ``[2B,4,H,W]``) + the five weights -> the channels-last stem input
+    ``[B,H,W,128]`` whose channels 0..39 / 40..79 hold the towers of image 1 / image 2 and whose channels 80..127 are zero
+    (``RingStemWide`` reads it as a 128-channel input of the direct kernels).  One transposing copy makes ``[2B,H,W,4]``; every
+    layer is ONE launch over 2B images; the fifth writes both slices of the wide buffer through its view, so the reference's
+    ``torch.cat`` is never a copy.  The five activations are kept for the backward (act' and weight-gradient inputs).
+
+    Backward: layers 5..1; the act' of layer i-1 sits in the epilogue of layer i's input gradient.  ``last``: the incoming gradient
+    is a true ``dL/dy`` and act' of the output is applied here; ``RingStemWide`` hands over the gradient of the PRE-activation
+    (the private convention of ``RingSegment``) and passes ``last = False``.  The image is data: no gradient is returned for it."""
+
+    @staticmethod
+    def forward(ctx, x, act, last, *weights):
+        B, _, H, W = x.shape
+        N = 2 * B
+        a = x.contiguous().view(N, 4, H, W).permute(0, 2, 3, 1).contiguous()
+        acts = [a]
+        ws = [weight_storage(w) for w in weights]
+        for i, (C, K) in enumerate(TOWER_PLAN):
+            if i < 4:
+                y, yv = _empty((N, H, W, K), torch.float32, x.device), _view(K)
+            else:
+                y, yv = _empty((B, H, W, TOWER_PITCH), torch.float32, x.device), _view(TOWER_PITCH, 0, 2)
+                y[..., TOWER_CHANNELS:].zero_()
+            tower_conv(a, ws[i], y, (N, H, W, C, K), _view(C), yv, act=act, epilogue=EPI_ACT if act else 0)
+            acts.append(y)
+            a = y
+        ctx.save_for_backward(*acts, *weights)
+        ctx.act, ctx.last = act, bool(last)
+        return a
+
+    @staticmethod
+    def backward(ctx, gy):
+        saved = ctx.saved_tensors
+        acts, weights = saved[:6], saved[6:]
+        act = ctx.act
+        B, H, W, _ = acts[5].shape
+        N = 2 * B
+        g = gy.contiguous()
+        if ctx.last:
+            if act == ACT["tanh"]:
+                g = g * (1.0 - acts[5] * acts[5])
+            elif act == ACT["relu"]:
+                g = g * (acts[5] > 0).to(g.dtype)
+        gv = _view(TOWER_PITCH, 0, 2)
+        grads = [None] * 5
+        for i in range(4, -1, -1):
+            C, K = TOWER_PLAN[i]
+            grads[i] = grad_for(tower_wgrad(acts[i], g, (N, H, W, C, K), _view(C), gv), weights[i])
+            if i:
+                gp = _empty((N, H, W, C), torch.float32, g.device)
+                tower_conv(g, weight_storage(weights[i]), gp, (N, H, W, K, C), gv, _view(C), act=act, epilogue=EPI_DACT if act else 0,
+                           dsrc=acts[i] if act else None, dsrc_view=_view(C) if act else None, transposed=True)
+                g, gv = gp, _view(C)
+        if BACKWARD_TRACE is not None:
+            BACKWARD_TRACE.append(("tower", 4, 40, 5))
+        return (None, None, None, *grads)
+
+
+class RingStemWide(torch.autograd.Function):
+    """The stem behind the feature tower: conv1 (80 -> 64, 3x3, stride (1,2)) + activation + the 3x3 / stride (1,2) max-pooling on
+    the tower's ``[N,H,W,128]`` buffer (channels 80..127 zero) -> ``[N,H,W/4,64]``.  conv1's weight is zero-padded to 128 input
+    channels per call (295 kB), so that forward, input gradient (``dl_conv2d_dgrad_strided_nhwc_f32``) and weight gradient
+    (``dl_conv2d_wgrad_nhwc_f32``) run on the direct kernels at C = 128, K = 64; the pooling kernels are those of ``RingStem``.
+    Unlike the 8-channel stem this one returns an input gradient.  ``dact_input``: the returned gradient is multiplied by act' of
+    the INPUT map in the input gradient's epilogue -- it is then the gradient of the tower's last pre-activation (what
+    ``RingTower`` with ``last = False`` expects); False returns the true ``dL/dx``.  Channels 80..127 of it are zero either way."""
+
+    @staticmethod
+    def forward(ctx, xw, w1, act, dact_input):
+        xw = xw.contiguous()
+        N, H, W, P = xw.shape
+        K, C = w1.shape[0], w1.shape[1]
+        w = torch.zeros((K, 3, 3, P), dtype=torch.float32, device=xw.device)
+        w[..., :C] = w1.detach().permute(0, 2, 3, 1)
+        a = conv_nhwc(xw, w, stride=(1, 2), act=act, epilogue=EPI_ACT if act else 0)
+        y, win = pool_fwd(a)
+        ctx.save_for_backward(xw, a, win, w, w1)
+        ctx.act, ctx.dact_input = act, bool(dact_input)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        xw, a, win, w, w1 = ctx.saved_tensors
+        N, H, W, P = xw.shape
+        C = w1.shape[1]
+        gc = pool_bwd(g.contiguous(), a, win, ctx.act)                     # gradient of conv1's pre-activation
+        # the first C input channels, dense in the parameter's own memory layout (AccumulateGrad and DDP's bucket views then take
+        # the gradient as it is instead of re-laying it out every step)
+        dw = wgrad_nhwc(xw, gc, 3, stride=(1, 2))[..., :C].permute(0, 3, 1, 2)
+        dw = dw.contiguous(memory_format=torch.channels_last if w1.is_contiguous(memory_format=torch.channels_last) and not w1.is_contiguous()
+                           else torch.contiguous_format)
+        gx = None
+        if ctx.needs_input_grad[0]:
+            fold = ctx.dact_input and ctx.act
+            gx = dgrad_strided(gc, w, (1, 2), (H, W), act=ctx.act, epilogue=EPI_DACT if fold else 0, dsrc=xw if fold else None)
+        if BACKWARD_TRACE is not None:
+            BACKWARD_TRACE.append(("stem_wide", C, w1.shape[0], 1))
+        return gx, dw, None, None
 
 
 # How the trunk is cut into autograd Functions.  Each Function hands its weight gradients to autograd when its backward has run, so

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
+#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), the narrow convolution family dl_tower_* (purely additive: the number stays), dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
 
 typedef void* dl_stream;
 
@@ -400,6 +400,41 @@ size_t dl_conv2d_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t 
                                        int32_t stride_h, int32_t stride_w);
 int dl_conv2d_wgrad_nhwc_f32(const float* x, const float* g, float* dw, void* workspace, int32_t N, int32_t H, int32_t W,
                              int32_t C, int32_t K, int32_t ksize, int32_t stride_h, int32_t stride_w, dl_stream stream);
+
+/*
+ * The NARROW family (csrc/tower.hip): the same 3x3, stride-1 ring convolution -- rows -1 and H read zeros, columns -1 and W read
+ * columns W-1 and 0, as addressing -- for FEW channels, on v_mfma_f32_16x16x4_f32 (exact fp32).  It serves the per-image feature
+ * tower of `pre_feature_extraction` (reference src/models/model.py:30-54: 4 -> 8 -> 16 -> 24 -> 32 -> 40 channels at full image
+ * resolution) and its autograd.  Channel domain: C % 4 == 0, K % 8 == 0, 4 <= C <= 64, 8 <= K <= 64 (DL_ERR_UNSUPPORTED otherwise).
+ * Any H >= 1 and W >= 1: tiles of 4 rows x 64 columns hang over the edges.
+ *
+ * VIEWS.  x, y, dsrc (and g of the weight gradient) are addressed through a view = three int32 {pitch, offset, group}:
+ *   element (image n, pixel p = h * W + w, channel c)  =  base[((n / group) * H * W + p) * pitch + offset + (n % group) * CH + c]
+ * with CH the tensor's own channel count (C for x; K for y, dsrc, g).  A dense [N][H][W][CH] tensor is {CH, 0, 1}.  {128, 0, 2}
+ * with K = 40 makes images 2b and 2b + 1 write channels 0..39 and 40..79 of pixel row b of a [N/2][H][W][128] buffer: the
+ * concatenation of the two towers of a sample is never a copy, and the backward reads its slices the same way.  Required:
+ * group >= 1, N % group == 0, pitch % 4 == 0, offset % 4 == 0, offset + group * CH <= pitch (DL_ERR_INVALID_ARGUMENT otherwise);
+ * (N / group) * H * W * pitch < 2^31 per view (DL_ERR_UNSUPPORTED beyond: 32-bit offsets).  Bases 16-byte aligned, as above.
+ * Only the CH channels of a view are read / written; the rest of a pixel's pitch is never touched.
+ *
+ *   dl_tower_conv3x3_nhwc_f32   y = epilogue(conv(x, w)).  w: transposed == 0: [K][3][3][C]; transposed == 1: [C][3][3][K], the
+ *       FORWARD weight of the layer whose input gradient is wanted (x = the output gradient), read with flipped taps, as
+ *       dl_conv2d_nhwc_f32 does.  epilogue: DL_CONV_ACT (v = act(v)) and / or DL_CONV_DACT (v *= act'(dsrc), dsrc = saved output of
+ *       the activation) with act 0 none, 1 tanh, 2 relu; any other flag, a bad act, a null x / w / y / x_view / y_view, or DACT
+ *       without dsrc and dsrc_view is DL_ERR_INVALID_ARGUMENT.  dsrc / dsrc_view may be NULL without DACT.
+ *   dl_tower_wgrad3x3_nhwc_f32  dw [K][3][3][C] = sum over pixels of g[pixel][k] * x[pixel + tap][c].  Every workgroup adds its four
+ *       waves in a fixed order and writes one partial dW to `workspace` (dl_tower_wgrad_workspace_bytes(N, H, W, C, K) bytes; the
+ *       query returns 0 for shapes the launch refuses); a second launch sums the partials in slab order.  No float atomics: the
+ *       result is bit-identical from run to run.  The workspace need not be initialised.  A null x / g / dw / workspace / view is
+ *       DL_ERR_INVALID_ARGUMENT.
+ * Both refuse through dl_last_error before any launch; no synchronisation, launches go to the caller's stream.
+ */
+int dl_tower_conv3x3_nhwc_f32(const float* x, const float* w, float* y, const float* dsrc, int32_t N, int32_t H, int32_t W,
+                              int32_t C, int32_t K, const int32_t* x_view, const int32_t* y_view, const int32_t* dsrc_view,
+                              int32_t transposed, int32_t act, uint32_t epilogue, dl_stream stream);
+size_t dl_tower_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t K);
+int dl_tower_wgrad3x3_nhwc_f32(const float* x, const float* g, float* dw, void* workspace, int32_t N, int32_t H, int32_t W,
+                               int32_t C, int32_t K, const int32_t* x_view, const int32_t* g_view, dl_stream stream);
 
 /*
  * The same stride-1 3x3 convolution (forward and, with the backward weight set, input gradient) as fused Winograd
