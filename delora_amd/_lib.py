@@ -94,10 +94,15 @@ SIGNATURES = {
     "dl_heads_bwd": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dl_heads_fwd_drop": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dl_heads_bwd_drop": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dl_heads_single_fwd": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dl_heads_single_bwd_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "dl_heads_single_bwd": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dl_dropout_scale_f32": (_i32, [_vp, _u32, ctypes.c_double, _i64, _vp, _vp]),
     "dl_stem_input_nhwc_drop_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, ctypes.c_double, _vp, _vp]),
     "dl_channel_scale_nhwc_t": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_channel_scale_bwd_act_nhwc_t": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "dl_tower_wide_drop_f32": (_i32, [_vp, _vp, ctypes.c_double, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "dl_tower_wide_drop_bwd_f32": (_i32, [_vp, _vp, _vp, ctypes.c_double, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_mean_hw_nhwc_h": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_mean_hw_bwd_act_h": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_conv2d_wgrad_h_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
@@ -127,6 +132,11 @@ WINO_BATCH = 16
 class HeadsParams(ctypes.Structure):
     """``dl_heads_params`` of include/delora_hip.h (ten pointers: parameters, or buffers for their gradients)."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("fc_w", "fc_b", "r1_w", "r1_b", "r3_w", "r3_b", "t1_w", "t1_b", "t3_w", "t3_b")]
+
+
+class HeadsSingleParams(ctypes.Structure):
+    """``dl_heads_single_params`` of include/delora_hip.h (six weights, six biases: parameters, or buffers for their gradients)."""
+    _fields_ = [("w", ctypes.c_void_p * 6), ("b", ctypes.c_void_p * 6)]
 
 
 class ConvHLayer(ctypes.Structure):

@@ -115,6 +115,45 @@ __global__ __launch_bounds__(256) void k_channel_scale_bwd_act(const void* __res
   }
 }
 
+// Site 1 behind the feature tower: y5 [2B][H][W][CH] (the compact, UN-dropped layer-5 output; image n = 2 b + k) -> xw [B][H][W][pitch], the
+// stem's wide input: channels k CH .. k CH + CH - 1 hold image k's tower times the mask, channels 2 CH .. pitch - 1 are written as zeros.  One
+// thread per 16-byte vector of xw.  Decision index = the flat index in the LOGICAL [B][H][W][2 CH] tensor (the pitch does not enter);
+// CH % 4 == 0, so a vector never straddles the two images and is one Philox call.
+__global__ __launch_bounds__(256) void k_tower_wide_drop(const float* __restrict__ y5, const uint64_t* __restrict__ seed, uint32_t thresh, float keep, long HW,
+                                                         int CH, int pq /* pitch / 4 */, long total, float* __restrict__ xw) {
+  const long v = (long)blockIdx.x * 256 + threadIdx.x;
+  if (v >= total) return;
+  const long pix = v / pq;
+  const int q = (int)(v % pq), dq = CH >> 1;                // dq: data vectors (= Philox calls) per pixel
+  f32x4 o = {0.f, 0.f, 0.f, 0.f};
+  if (q < dq) {
+    const int c = q * 4, k = c >= CH ? 1 : 0;
+    const long b = pix / HW, hw = pix % HW;
+    const f32x4 a = *(const f32x4*)(y5 + (size_t)((2 * b + k) * HW + hw) * CH + (c - k * CH));
+    o = a * dr_scales4((uint64_t)pix * dq + q, 1u, seed[0], thresh, keep);
+  }
+  ((f32x4*)xw)[v] = o;
+}
+
+// backward of k_tower_wide_drop: g5[n][h][w][c] = (gx[b][h][w][k CH + c] * s(i)) * act'(y5[n][h][w][c]), the mask regenerated from the seed.
+// One thread per 16-byte vector of g5; channels 2 CH .. pitch - 1 of gx are never read.
+__global__ __launch_bounds__(256) void k_tower_wide_drop_bwd(const float* __restrict__ gx, const float* __restrict__ y5, const uint64_t* __restrict__ seed,
+                                                             uint32_t thresh, float keep, int act, long HW, int CH, int pitch, long total,
+                                                             float* __restrict__ g5) {
+  const long v = (long)blockIdx.x * 256 + threadIdx.x;
+  if (v >= total) return;
+  const int cq = CH >> 2, q = (int)(v % cq);
+  const long np = v / cq, n = np / HW, hw = np % HW;        // np: pixel of the compact tensor
+  const long pix = (n >> 1) * HW + hw;
+  const int k = (int)(n & 1);
+  const f32x4 g = *(const f32x4*)(gx + (size_t)pix * pitch + k * CH + q * 4), a = ((const f32x4*)y5)[v];
+  const f32x4 s = dr_scales4((uint64_t)pix * (CH >> 1) + k * cq + q, 1u, seed[0], thresh, keep);
+  f32x4 o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = (g[j] * s[j]) * ch_dact(a[j], act);
+  ((f32x4*)g5)[v] = o;
+}
+
 // round(p 2^32) and 1.0f / (1.0f - p); p in [0, 1)
 static int dr_params(const char* who, double p, uint32_t* thresh, float* keep) {
   if (!(p >= 0.0) || !(p < 1.0)) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: p must lie in [0, 1)", who);
@@ -183,4 +222,37 @@ extern "C" int dl_channel_scale_bwd_act_nhwc_t(const void* g, const void* x, con
   else if (dtype == DL_DTYPE_F16) hipLaunchKernelGGL(k_channel_scale_bwd_act<1>, grid, dim3(256), 0, st, g, x, scale, per, cvecs, (int)C, (int)act, total, g_pre);
   else hipLaunchKernelGGL(k_channel_scale_bwd_act<2>, grid, dim3(256), 0, st, g, x, scale, per, cvecs, (int)C, (int)act, total, g_pre);
   return dl_check_launch("dl_channel_scale_bwd_act_nhwc_t");
+}
+
+static int dr_tower_check(const char* who, const void* a, const void* b, const void* c, const void* d, int B, int H, int W, int CH, int pitch) {
+  if (!a || !b || !c || !d) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
+  if (B <= 0 || H <= 0 || W <= 0 || CH <= 0 || CH % 4 || pitch % 4 || 2 * (long)CH > pitch)
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad size (CH %% 4 == 0, pitch %% 4 == 0, 2 CH <= pitch): B=%d H=%d W=%d CH=%d pitch=%d", who, B, H, W, CH, pitch);
+  if ((long)B * H * W * pitch >= (1L << 31)) return dl_fail(DL_ERR_UNSUPPORTED, "%s: the wide buffer would pass 2^31 elements", who);
+  return DL_OK;
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_tower_wide_drop_f32(const float* y5, const uint64_t* seed, double p, int32_t B, int32_t H, int32_t W, int32_t CH, int32_t pitch,
+                                      float* xw, dl_stream stream) {
+  if (int rc = dr_tower_check("dl_tower_wide_drop_f32", y5, seed, xw, xw, B, H, W, CH, pitch)) return rc;
+  uint32_t thresh; float keep;
+  if (int rc = dr_params("dl_tower_wide_drop_f32", p, &thresh, &keep)) return rc;
+  const long HW = (long)H * W, total = (long)B * HW * (pitch / 4);
+  hipLaunchKernelGGL(k_tower_wide_drop, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y5, seed, thresh, keep, HW, (int)CH,
+                     (int)(pitch / 4), total, xw);
+  return dl_check_launch("dl_tower_wide_drop_f32");
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_tower_wide_drop_bwd_f32(const float* gx, const float* y5, const uint64_t* seed, double p, int32_t act, int32_t B, int32_t H, int32_t W,
+                                          int32_t CH, int32_t pitch, float* g5, dl_stream stream) {
+  if (int rc = dr_tower_check("dl_tower_wide_drop_bwd_f32", gx, y5, seed, g5, B, H, W, CH, pitch)) return rc;
+  if (act < 0 || act > 2) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_tower_wide_drop_bwd_f32: act outside 0..2");
+  uint32_t thresh; float keep;
+  if (int rc = dr_params("dl_tower_wide_drop_bwd_f32", p, &thresh, &keep)) return rc;
+  const long HW = (long)H * W, total = 2L * B * HW * (CH / 4);
+  hipLaunchKernelGGL(k_tower_wide_drop_bwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gx, y5, seed, thresh, keep,
+                     (int)act, HW, (int)CH, (int)pitch, total, g5);
+  return dl_check_launch("dl_tower_wide_drop_bwd_f32");
 }

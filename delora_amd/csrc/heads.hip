@@ -334,3 +334,180 @@ extern "C" int dl_heads_bwd_drop(const float* x, const dl_heads_params* params, 
   return heads_bwd("dl_heads_bwd_drop", x, params, B, F, R, Hd, act, fc_scale, a1, a2, rot_raw, norm, grad_translation, grad_rotation, grads,
                    grad_x, workspace, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// The single-MLP head (reference src/models/model.py:59-72, :106-114; `use_single_mlp_at_output`): fc -> [act, Linear] x 5 -> 7 outputs,
+// rotation = y[:, :4] / ||y[:, :4]||_F (ONE norm over the whole batch), translation = y[:, 4:].  Layer l = 0..5 is w[l] [n_{l+1}][n_l] with
+// n = (F, R, H1, H2, H3, H4, 7).  Forward: k_heads_rows per hidden layer (nmat = 1) + k_heads_single_out: six launches.  Backward:
+// k_heads_single_out_bwd, then per layer 4..0 the dense backward k_heads_fc_bwd (dW, db, per-chunk partial input gradients) and a reduction of
+// the partials in chunk order that applies act' of the layer's input (and the fc mask's own factor on layer 1's): eleven launches.
+struct HeadsSingleP { const float* w[6]; const float* b[6]; };
+
+// a4 [B][K] -> raw = a4 w5^T + b5 [B][7]: rot_raw [B][4], translation [B][3], rotation = rot_raw / norm, norm [1]
+__global__ __launch_bounds__(256) void k_heads_single_out(const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias, int B, int K,
+                                                          float* __restrict__ rot_raw, float* __restrict__ translation, float* __restrict__ rotation,
+                                                          float* __restrict__ norm) {
+  __shared__ float raw[HD_MAXB * 7];
+  __shared__ float nrm;
+  const int t = threadIdx.x;
+  if (t < B * 7) {
+    const int b = t / 7, i = t % 7;
+    const float* wr = w + (size_t)i * K;
+    const float* ar = a + (size_t)b * K;
+    float s = 0.f;
+    for (int m = 0; m < K; ++m) s = fmaf(ar[m], wr[m], s);
+    raw[t] = s + bias[i];
+  }
+  __syncthreads();
+  if (t == 0) {
+    float s = 0.f;
+    for (int b = 0; b < B; ++b)
+      for (int i = 0; i < 4; ++i) s = fmaf(raw[b * 7 + i], raw[b * 7 + i], s);
+    nrm = sqrtf(s);
+    norm[0] = nrm;
+  }
+  __syncthreads();
+  if (t < B * 7) {
+    const int b = t / 7, i = t % 7;
+    if (i < 4) { rot_raw[b * 4 + i] = raw[t]; rotation[b * 4 + i] = raw[t] / nrm; }
+    else translation[b * 3 + (i - 4)] = raw[t];
+  }
+}
+
+// backward of k_heads_single_out: d_w5 [7][K], d_b5 [7], gh [B][K] = dL/d(pre-activation of the last hidden layer)
+__global__ __launch_bounds__(256) void k_heads_single_out_bwd(const float* __restrict__ a, const float* __restrict__ w, int B, int K, int act,
+                                                              const float* __restrict__ rot_raw, const float* __restrict__ norm, const float* __restrict__ g_tr,
+                                                              const float* __restrict__ g_rotn, float* __restrict__ d_w, float* __restrict__ d_b,
+                                                              float* __restrict__ gh) {
+  __shared__ float g[HD_MAXB * 7];            // dL/d(raw outputs): rotation (4) then translation (3) per sample
+  __shared__ float dot;
+  const int t = threadIdx.x;
+  const float n = norm[0];
+  if (t == 0) {                               // y = r / n over ALL elements: dL/dr = (g - y (y . g)) / n
+    float s = 0.f;
+    for (int b = 0; b < B; ++b)
+      for (int i = 0; i < 4; ++i) s = fmaf(g_rotn[b * 4 + i], rot_raw[b * 4 + i] / n, s);
+    dot = s;
+  }
+  __syncthreads();
+  if (t < B * 7) {
+    const int b = t / 7, i = t % 7;
+    g[t] = i < 4 ? (g_rotn[b * 4 + i] - (rot_raw[b * 4 + i] / n) * dot) / n : g_tr[b * 3 + (i - 4)];
+  }
+  __syncthreads();
+  for (int q = t; q < 7 * K; q += blockDim.x) {
+    const int i = q / K, m = q % K;
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s = fmaf(g[b * 7 + i], a[(size_t)b * K + m], s);
+    d_w[q] = s;
+  }
+  if (t < 7) {
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += g[b * 7 + t];
+    d_b[t] = s;
+  }
+  for (int q = t; q < B * K; q += blockDim.x) {
+    const int m = q % K, b = q / K;
+    float s = 0.f;
+    for (int i = 0; i < 7; ++i) s = fmaf(g[b * 7 + i], w[(size_t)i * K + m], s);
+    gh[q] = s * hd_dact(a[q], act);
+  }
+}
+
+// k_heads_gx_reduce for a layer whose input x [n] is an activated map: gx[i] = (sum_k part[k][i]) * act'(x[i]) (* scale[i]: the fc mask)
+__global__ __launch_bounds__(256) void k_heads_gx_reduce_act(const float* __restrict__ part, int chunks, int n, const float* __restrict__ x, int act,
+                                                             const float* __restrict__ scale /* [n] or null */, float* __restrict__ gx) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float s = 0.f;
+  for (int k = 0; k < chunks; ++k) s += part[(size_t)k * n + i];
+  float go = s * hd_dact(x[i], act);
+  if (scale) go *= scale[i];
+  gx[i] = go;
+}
+
+static int heads_single_check(const char* who, const dl_heads_single_params* p, int B, const int n[7], int act) {
+  if (!p) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
+  for (int l = 0; l < 6; ++l)
+    if (!p->w[l] || !p->b[l]) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
+  bool ok = B > 0 && B <= HD_MAXB && act >= 0 && act <= 2;
+  for (int l = 0; l < 6; ++l) ok = ok && n[l] > 0 && n[l] <= (1 << 20);
+  if (!ok) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad size (1 <= B <= %d, every width >= 1) or activation", who, HD_MAXB);
+  return DL_OK;
+}
+static size_t heads_single_part_floats(int B, const int n[7]) {
+  size_t m = 0;
+  for (int l = 0; l < 5; ++l) {
+    const size_t f = (size_t)((n[l + 1] + HD_JC - 1) / HD_JC) * B * n[l];
+    if (f > m) m = f;
+  }
+  return m;
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_heads_single_fwd(const float* x, const dl_heads_single_params* params, int32_t B, int32_t F, int32_t R, int32_t H1, int32_t H2,
+                                   int32_t H3, int32_t H4, int32_t act, const float* fc_scale, float* acts, float* rot_raw, float* translation,
+                                   float* rotation, float* norm, dl_stream stream) {
+  const char* who = "dl_heads_single_fwd";
+  const int n[7] = {F, R, H1, H2, H3, H4, 7};
+  if (!x || !acts || !rot_raw || !translation || !rotation || !norm) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
+  if (int rc = heads_single_check(who, params, B, n, act)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const float* in = x;
+  float* out = acts;
+  for (int l = 0; l < 5; ++l) {
+    const int K = n[l], rows = n[l + 1], kc = heads_kc(B, K);
+    hipLaunchKernelGGL(k_heads_rows, dim3((rows + 3) / 4), dim3(256), (size_t)B * kc * sizeof(float), st, in, (int)B, K, params->w[l], params->b[l],
+                       (const float*)nullptr, (const float*)nullptr, rows, 1, (int)act, kc, l == 0 ? fc_scale : (const float*)nullptr, out);
+    in = out;
+    out += (size_t)B * rows;
+  }
+  hipLaunchKernelGGL(k_heads_single_out, dim3(1), dim3(256), 0, st, in, params->w[5], params->b[5], (int)B, (int)H4, rot_raw, translation, rotation, norm);
+  return dl_check_launch(who);
+}
+
+/* see include/delora_hip.h */
+extern "C" size_t dl_heads_single_bwd_workspace_bytes(int32_t B, int32_t F, int32_t R, int32_t H1, int32_t H2, int32_t H3, int32_t H4) {
+  const int n[7] = {F, R, H1, H2, H3, H4, 7};
+  if (B <= 0 || B > HD_MAXB) return 0;
+  for (int l = 0; l < 6; ++l)
+    if (n[l] <= 0 || n[l] > (1 << 20)) return 0;
+  // the gradients of the five pre-activations [B][R + H1 + H2 + H3 + H4], then the per-chunk partial input gradients of the largest layer
+  return ((size_t)B * ((size_t)R + H1 + H2 + H3 + H4) + heads_single_part_floats(B, n)) * sizeof(float);
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_heads_single_bwd(const float* x, const dl_heads_single_params* params, int32_t B, int32_t F, int32_t R, int32_t H1, int32_t H2,
+                                   int32_t H3, int32_t H4, int32_t act, const float* fc_scale, const float* acts, const float* rot_raw,
+                                   const float* norm, const float* grad_translation, const float* grad_rotation,
+                                   const dl_heads_single_params* grads, float* grad_x, void* workspace, dl_stream stream) {
+  const char* who = "dl_heads_single_bwd";
+  const int n[7] = {F, R, H1, H2, H3, H4, 7};
+  if (!x || !acts || !rot_raw || !norm || !grad_translation || !grad_rotation || !grad_x || !workspace)
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
+  if (int rc = heads_single_check(who, params, B, n, act)) return rc;
+  if (int rc = heads_single_check(who, grads, B, n, act)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const float* a[5];                           // a[l] = the activated output of layer l
+  float* g[5];                                 // g[l] = the gradient of layer l's pre-activation
+  {
+    const float* ap = acts;
+    float* gp = (float*)workspace;
+    for (int l = 0; l < 5; ++l) { a[l] = ap; g[l] = gp; ap += (size_t)B * n[l + 1]; gp += (size_t)B * n[l + 1]; }
+  }
+  float* part = (float*)workspace + (size_t)B * ((size_t)R + H1 + H2 + H3 + H4);
+  hipLaunchKernelGGL(k_heads_single_out_bwd, dim3(1), dim3(256), 0, st, a[4], params->w[5], (int)B, (int)H4, (int)act, rot_raw, norm, grad_translation,
+                     grad_rotation, (float*)grads->w[5], (float*)grads->b[5], g[4]);
+  for (int l = 4; l >= 0; --l) {               // layer l: input n[l] wide (x or a[l-1]), output n[l+1] wide
+    const int K = n[l], M = n[l + 1], chunks = (M + HD_JC - 1) / HD_JC;
+    const float* in = l ? a[l - 1] : x;
+    hipLaunchKernelGGL(k_heads_fc_bwd, dim3((K + 255) / 256, chunks), dim3(256), 0, st, in, (const float*)g[l], params->w[l], (int)B, K, M,
+                       (float*)grads->w[l], (float*)grads->b[l], part);
+    if (l)
+      hipLaunchKernelGGL(k_heads_gx_reduce_act, dim3((B * K + 255) / 256), dim3(256), 0, st, (const float*)part, chunks, B * K, in, (int)act,
+                         l == 1 ? fc_scale : (const float*)nullptr, g[l - 1]);
+    else
+      hipLaunchKernelGGL(k_heads_gx_reduce, dim3((B * K + 255) / 256), dim3(256), 0, st, (const float*)part, chunks, B * K, grad_x);
+  }
+  return dl_check_launch(who);
+}

@@ -37,10 +37,7 @@ class Deployer(object):
             # when every configured image size actually takes that path: the module path (library convolutions on NCHW
             # activations) would re-lay-out channels_last weights or activations on every call.
             sizes = [(config[d]["vertical_cells"], config[d]["horizontal_cells"]) for d in config["datasets"]]
-            # (behind the feature tower the HIP path needs inactive dropout: that combination trains on the module stem and keeps
-            # the default weight layout; in eval mode such a model does take the HIP path and pays one re-laying copy per weight and call)
-            tower_on_modules = config.get("pre_feature_extraction", False) and config.get("use_dropout", False)
-            if not tower_on_modules and all(self.model.resnet.hip_path_takes(H, W) for (H, W) in sizes):
+            if all(self.model.resnet.hip_path_takes(H, W) for (H, W) in sizes):
                 self.model.resnet.trunk_weights_channels_last()
         if config["use_jit"]:
             first = config["datasets"][0]

@@ -50,25 +50,39 @@ class OdometryModel(torch.nn.Module):
     def _tower_weights(self):
         return [m.weight for m in self.feature_extractor if isinstance(m, torch.nn.Conv2d)]
 
+    def _fused(self, pooled, fc_scale):
+        """fc + heads as ONE autograd Function on the pooled feature: ``FusedHeads`` for the two heads, ``FusedHeadsSingle`` for
+        ``use_single_mlp_at_output``; ``fc_scale`` (the dropout mask of the fc output, or None) travels into either as a factor."""
+        act = 2 if self.config["activation_fct"] == "relu" else 1
+        extra = [fc_scale] if fc_scale is not None else []
+        with torch.autocast("cuda", enabled=False):
+            if self.config["use_single_mlp_at_output"]:
+                linears = [m for m in self.fully_connected_rot_trans if isinstance(m, torch.nn.Linear)]
+                params = [self.resnet.fc.weight, self.resnet.fc.bias] + [t for m in linears for t in (m.weight, m.bias)]
+                return model_parts.FusedHeadsSingle.apply(pooled.float(), act, *params, *extra)
+            fr, ft = self.fully_connected_rotation, self.fully_connected_translation
+            return model_parts.FusedHeads.apply(pooled.float(), act, self.resnet.fc.weight, self.resnet.fc.bias, fr[1].weight, fr[1].bias,
+                                                fr[3].weight, fr[3].bias, ft[1].weight, ft[1].bias, ft[3].weight, ft[3].bias, *extra)
+
     def forward_tower(self, stacked):
         """``pre_feature_extraction`` on the HIP path: the planar pair ``[B,8,H,W]`` through ``ring_conv.RingTower`` (five narrow MFMA
-        layers per image, both images per launch), ``RingStemWide``, the trunk and the fused heads.  Returns None when that path does
-        not take the input (``ResNetModified.wide_path_dtype``: CPU tensors, narrow networks, widths not divisible by 4, active
-        dropout, ``cnn_impl: modules``); ``cnn_impl: hip`` makes that an error."""
+        layers per image, both images per launch; ``RingTowerDrop`` with active dropout), ``RingStemWide``, the trunk and the fused
+        heads.  Returns None when that path does not take the input (``ResNetModified.wide_path_dtype``: CPU tensors, narrow networks,
+        widths not divisible by 4, ``cnn_impl: modules``); ``cnn_impl: hip`` makes that an error."""
         dtype = self.resnet.wide_path_dtype(stacked)
         if dtype is None:
             if self.config.get("cnn_impl", "auto") == "hip" and stacked.is_cuda:
-                raise RuntimeError(f"cnn_impl 'hip': the HIP feature tower does not support input {tuple(stacked.shape)} / dtype {stacked.dtype}"
-                                   + (" with active dropout" if self.resnet.dropout_active() else ""))
+                raise RuntimeError(f"cnn_impl 'hip': the HIP feature tower does not support input {tuple(stacked.shape)} / dtype {stacked.dtype} "
+                                   "(it takes fp32 pairs of a full-width network whose width is a multiple of 4)")
             return None                      # (the resnet prints the one module-path note for its 80-channel input)
-        pooled, _ = self.resnet.pooled_features_wide(stacked, self._tower_weights(), dtype)
+        pooled, _, fc_scale = self.resnet.pooled_features_wide(stacked, self._tower_weights(), dtype)
+        if self._fused_heads_ok(stacked):
+            return self._fused(pooled, fc_scale)
         with torch.autocast("cuda", enabled=False):
-            if self._fused_heads_ok(stacked):
-                act = 2 if self.config["activation_fct"] == "relu" else 1
-                fr, ft = self.fully_connected_rotation, self.fully_connected_translation
-                return model_parts.FusedHeads.apply(pooled.float(), act, self.resnet.fc.weight, self.resnet.fc.bias, fr[1].weight, fr[1].bias,
-                                                    fr[3].weight, fr[3].bias, ft[1].weight, ft[1].bias, ft[3].weight, ft[3].bias)
-            return self._heads(self.resnet.fc(pooled))
+            out = self.resnet.fc(pooled)
+            if fc_scale is not None:
+                out = out * fc_scale                                # the same mask the fused heads would apply
+            return self._heads(out)
 
     def forward_features(self, image_1, image_2):
         if self.pre_feature_extraction:
@@ -79,25 +93,20 @@ class OdometryModel(torch.nn.Module):
 
     def forward_stacked(self, stacked):
         """Same as forward() for an already channel-stacked ``[B,8,H,W]`` pair (no concatenation copy).  When the CNN runs on the HIP
-        stem + trunk, fc and the two heads run as ``model_parts.FusedHeads`` (csrc/heads.hip: 3 + 4 launches instead of ~45); with active
-        dropout the fc output's mask travels into them as a factor."""
+        stem + trunk, fc and the heads run as ``model_parts.FusedHeads`` (csrc/heads.hip: 3 + 4 launches instead of ~45) or, for
+        ``use_single_mlp_at_output``, as ``model_parts.FusedHeadsSingle`` (6 + 11 instead of ~65); with active dropout the fc output's
+        mask travels into them as a factor."""
         if self._fused_heads_ok(stacked):
             pooled, _, fc_scale = self.resnet.pooled_features_drop(stacked)
             if pooled is not None:
-                act = 2 if self.config["activation_fct"] == "relu" else 1
-                fr, ft = self.fully_connected_rotation, self.fully_connected_translation
-                with torch.autocast("cuda", enabled=False):
-                    translation, rotation = model_parts.FusedHeads.apply(
-                        pooled.float(), act, self.resnet.fc.weight, self.resnet.fc.bias, fr[1].weight, fr[1].bias, fr[3].weight, fr[3].bias,
-                        ft[1].weight, ft[1].bias, ft[3].weight, ft[3].bias, *([fc_scale] if fc_scale is not None else []))
-                return translation, rotation
+                return self._fused(pooled, fc_scale)
         feat = self.resnet(stacked)[-1]
         return self._heads(feat)
 
     def _fused_heads_ok(self, x):
-        """fc + heads as one fused Function: CUDA input, the default two-head architecture, a batch of at most 16 (dropout on the fc
-        output is a factor inside the fused kernels: ``dl_heads_fwd_drop``)."""
-        return (x.is_cuda and not self.config["use_single_mlp_at_output"] and x.shape[0] <= 16 and self.config.get("fused_heads", True)
+        """fc + heads as one fused Function (either head architecture): CUDA input, a batch of at most 16 (dropout on the fc output
+        is a factor inside the fused kernels: ``dl_heads_fwd_drop``, the ``fc_scale`` of ``dl_heads_single_fwd``)."""
+        return (x.is_cuda and x.shape[0] <= 16 and self.config.get("fused_heads", True)
                 and self.config.get("cnn_impl", "auto") != "modules")
 
     def _heads(self, feat):

@@ -167,3 +167,81 @@ class FusedHeads(torch.autograd.Function):
         _lib.check(lib.dl_heads_bwd_drop(vp(x), ctypes.byref(st), B, F, R, Hd, ctx.act, vp(fc_scale), vp(a1), vp(a2), vp(rot_raw), vp(norm), vp(gt),
                                          vp(gr), ctypes.byref(gs), vp(gx), vp(ws), stream), "dl_heads_bwd_drop")
         return (gx, None, *grads, None)
+
+
+class FusedHeadsSingle(torch.autograd.Function):
+    """fc -> the single five-layer MLP of ``use_single_mlp_at_output`` -> whole-batch quaternion norm as ``dl_heads_single_fwd`` /
+    ``dl_heads_single_bwd`` (csrc/heads.hip): six launches forward and eleven backward instead of ~65 small library launches
+    (reference: src/models/model.py:59-72 the MLP, :106-114 the slice and the norm).  ``forward(x [B,F], act, fc.w, fc.b, then weight
+    and bias of the five Linear layers) -> (translation [B,3], rotation [B,4])``; fp32 CUDA tensors, B <= 16.  An optional thirteenth
+    tensor ``fc_scale [B,R]`` is the dropout mask of the fc output, as in ``FusedHeads``.  Gradients come back in the order of the
+    arguments, each in its parameter's shape."""
+
+    @staticmethod
+    def _struct(tensors):
+        from .. import _lib
+        st = _lib.HeadsSingleParams()
+        for l in range(6):
+            st.w[l], st.b[l] = tensors[2 * l].data_ptr(), tensors[2 * l + 1].data_ptr()
+        return st
+
+    @staticmethod
+    def _sizes(x, params):
+        widths = [x.shape[1]] + [params[2 * l].shape[0] for l in range(6)]
+        for l in range(6):
+            if tuple(params[2 * l].shape) != (widths[l + 1], widths[l]) or tuple(params[2 * l + 1].shape) != (widths[l + 1],):
+                raise ValueError(f"layer {l}: weight {tuple(params[2 * l].shape)} / bias {tuple(params[2 * l + 1].shape)} do not continue the chain")
+        if widths[6] != 7:
+            raise ValueError(f"the last layer must have 7 outputs (quaternion + translation), got {widths[6]}")
+        return widths[:6]
+
+    @staticmethod
+    def forward(ctx, x, act, *params):
+        import ctypes
+        from .. import _lib
+        lib = _lib.load()
+        x = x.contiguous()
+        fc_scale = params[12].contiguous() if len(params) > 12 else None
+        params = tuple(p.contiguous() for p in params[:12])
+        B = x.shape[0]
+        sizes = FusedHeadsSingle._sizes(x, params)                                    # F, R, H1..H4
+        R = sizes[1]
+        dev = x.device
+        if fc_scale is not None and (tuple(fc_scale.shape) != (B, R) or fc_scale.dtype != torch.float32):
+            raise ValueError(f"fc_scale must be fp32 [{B},{R}], got {tuple(fc_scale.shape)} {fc_scale.dtype}")
+        acts = torch.empty((B * sum(sizes[1:]),), dtype=torch.float32, device=dev)
+        small = torch.empty((B * 4 + 1,), dtype=torch.float32, device=dev)           # rot_raw [B,4] | norm (outputs stay tensors of their own)
+        rot_raw, norm = small[:4 * B].view(B, 4), small[4 * B:]
+        translation = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        rotation = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        st = FusedHeadsSingle._struct(params)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)          # noqa: E731
+        _lib.check(lib.dl_heads_single_fwd(vp(x), ctypes.byref(st), B, *sizes, int(act), vp(fc_scale), vp(acts), vp(rot_raw), vp(translation),
+                                           vp(rotation), vp(norm), stream), "dl_heads_single_fwd")
+        ctx.act, ctx.sizes = int(act), sizes
+        ctx.has_scale = fc_scale is not None
+        ctx.save_for_backward(x, acts, small, *params, *([fc_scale] if fc_scale is not None else []))
+        return translation, rotation
+
+    @staticmethod
+    def backward(ctx, g_translation, g_rotation):
+        import ctypes
+        from .. import _lib
+        lib = _lib.load()
+        x, acts, small, *params = ctx.saved_tensors
+        fc_scale = params.pop() if ctx.has_scale else None
+        B = x.shape[0]
+        rot_raw, norm = small[:4 * B], small[4 * B:]
+        dev = x.device
+        gt = (g_translation if g_translation is not None else torch.zeros((B, 3), device=dev)).contiguous().float()
+        gr = (g_rotation if g_rotation is not None else torch.zeros((B, 4), device=dev)).contiguous().float()
+        grads = [torch.empty_like(p) for p in params]
+        gx = torch.empty_like(x)
+        ws = torch.empty((lib.dl_heads_single_bwd_workspace_bytes(B, *ctx.sizes) // 4,), dtype=torch.float32, device=dev)
+        st, gs = FusedHeadsSingle._struct(params), FusedHeadsSingle._struct(grads)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)          # noqa: E731
+        _lib.check(lib.dl_heads_single_bwd(vp(x), ctypes.byref(st), B, *ctx.sizes, ctx.act, vp(fc_scale), vp(acts), vp(rot_raw), vp(norm), vp(gt),
+                                           vp(gr), ctypes.byref(gs), vp(gx), vp(ws), stream), "dl_heads_single_bwd")
+        return (gx, None, *grads) + ((None,) if ctx.has_scale else ())

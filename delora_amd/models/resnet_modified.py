@@ -132,7 +132,7 @@ class ResNetModified(torch.nn.Module):
             seen.add(key)
             why = why or ("autocast shapes do not tile (csrc/convh.hip)" if key[2]
                           else "channel counts are not multiples of 64, or the width is not a multiple of 4"
-                          + (" (active dropout needs the HIP stem as well as the trunk)" if key[3] else ""))
+                          + (" (with dropout the HIP stem has to take the input as well as the trunk)" if key[3] else ""))
             print(f"[delora_amd] CNN input {key[0]} {str(x.dtype).replace('torch.', '')} runs on the MODULE path (library convolutions), "
                   f"not on the HIP stem + trunk: {why}", flush=True)
 
@@ -226,10 +226,10 @@ class ResNetModified(torch.nn.Module):
 
     def wide_path_dtype(self, stacked, pair=False):
         """Whether the planar image pair ``[B,8,H,W]`` of a network behind the feature tower runs on the HIP tower + wide stem + trunk:
-        an fp32 CUDA tensor, a full-width network with 80 input channels, a width divisible by 4, no active dropout.  Returns None
+        an fp32 CUDA tensor, a full-width network with 80 input channels, a width divisible by 4 (with or without dropout).  Returns None
         (no), torch.float32, or -- inside ``torch.autocast`` -- the half-precision dtype the trunk then runs in.  ``pair``: ``stacked``
         is the first ``[B,4,H,W]`` image of a pair that has not been concatenated yet (a shape test before the copy)."""
-        if (self.impl == "modules" or not stacked.is_cuda or stacked.dtype != torch.float32 or self.dropout_active()
+        if (self.impl == "modules" or not stacked.is_cuda or stacked.dtype != torch.float32
                 or self.conv1.in_channels != ring_conv.TOWER_CHANNELS or stacked.dim() != 4):
             return None
         B, C, H, W = stacked.shape
@@ -247,16 +247,26 @@ class ResNetModified(torch.nn.Module):
     def pooled_features_wide(self, stacked, tower_weights, dtype):
         """The globally pooled feature ``[B,C']`` (fp32) of an image pair behind the feature tower, all on HIP kernels: ``RingTower``
         and ``RingStemWide`` in fp32 (inside autocast too, as the 8-channel stem), then the trunk in ``dtype`` (``wide_path_dtype``).
-        Returns (feat, last feature map as NCHW view or None)."""
+        Returns (feat, last feature map as NCHW view or None, fc scale or None).  With active dropout one seed is drawn per call and
+        serves the three sites: the element-wise mask on the 80 tower channels inside ``RingTowerDrop``, the channel mask behind
+        layer3 in the trunk, and the scale ``[B,R]`` for the fc output that goes back to the caller (as ``pooled_features_drop``)."""
         act = ring_conv.ACT["relu" if self.activation_fct == "relu" else "tanh"]
         blocks, weights = self._trunk_blocks()
         with torch.autocast("cuda", enabled=False):
+            if self.dropout_active():
+                (seed, p), d_ch, fc_scale = self._draw_dropout(stacked, self.layer3[-1].conv2.out_channels)
+                xw = ring_conv.RingTowerDrop.apply(stacked, act, seed, p, *tower_weights)   # [B,H,W,128]: dropped, channels 80.. zero
+                x0 = ring_conv.RingStemWide.apply(xw, self.conv1.weight, act, False)        # (False: the true dL/dxw goes back)
+                if dtype != torch.float32:
+                    return ring_conv.ring_trunk_h(x0, act, blocks, dtype, weights, channel_drop=d_ch), None, fc_scale
+                x4 = ring_conv.ring_trunk(x0, act, blocks, weights, channel_drop=d_ch)
+                return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), fc_scale
             xw = ring_conv.RingTower.apply(stacked, act, False, *tower_weights)            # [B,H,W,128], channels 80.. zero
             x0 = ring_conv.RingStemWide.apply(xw, self.conv1.weight, act, True)             # [B,H,W/4,C0]
             if dtype != torch.float32:
-                return ring_conv.RingTrunkH.apply(x0, act, blocks, dtype, *weights), None
+                return ring_conv.RingTrunkH.apply(x0, act, blocks, dtype, *weights), None, None
             x4 = ring_conv.RingTrunk.apply(x0, act, blocks, *weights)
-            return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2)
+            return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), None
 
     def forward(self, x):
         act = "relu" if self.activation_fct == "relu" else "tanh"

@@ -543,6 +543,22 @@ def tower_supported(x_shape):
     return C == 8 and B >= 1 and H >= 1 and W >= 1 and B * H * W * TOWER_PITCH < (1 << 31)
 
 
+def _tower_backward(g, gv, acts, weights, act, N, H, W):
+    """Layers 5..1 of the tower's backward from ``g`` = the gradient of layer 5's PRE-activation, laid out as the view ``gv``: per
+    layer the weight gradient, then the input gradient with act' of the layer below in its epilogue.  Returns the five weight
+    gradients in the parameters' layout."""
+    grads = [None] * 5
+    for i in range(4, -1, -1):
+        C, K = TOWER_PLAN[i]
+        grads[i] = grad_for(tower_wgrad(acts[i], g, (N, H, W, C, K), _view(C), gv), weights[i])
+        if i:
+            gp = _empty((N, H, W, C), torch.float32, g.device)
+            tower_conv(g, weight_storage(weights[i]), gp, (N, H, W, K, C), gv, _view(C), act=act, epilogue=EPI_DACT if act else 0,
+                       dsrc=acts[i] if act else None, dsrc_view=_view(C) if act else None, transposed=True)
+            g, gv = gp, _view(C)
+    return grads
+
+
 class RingTower(torch.autograd.Function):
     """The five 3x3 ring convolutions + activation in front of the pose CNN (reference src/models/model.py:30-54), for both images
     of every sample at once: planar ``[B,8,H,W]`` (= ``[2B,4,H,W]``) + the five weights -> the channels-last stem input
@@ -588,19 +604,55 @@ class RingTower(torch.autograd.Function):
                 g = g * (1.0 - acts[5] * acts[5])
             elif act == ACT["relu"]:
                 g = g * (acts[5] > 0).to(g.dtype)
-        gv = _view(TOWER_PITCH, 0, 2)
-        grads = [None] * 5
-        for i in range(4, -1, -1):
-            C, K = TOWER_PLAN[i]
-            grads[i] = grad_for(tower_wgrad(acts[i], g, (N, H, W, C, K), _view(C), gv), weights[i])
-            if i:
-                gp = _empty((N, H, W, C), torch.float32, g.device)
-                tower_conv(g, weight_storage(weights[i]), gp, (N, H, W, K, C), gv, _view(C), act=act, epilogue=EPI_DACT if act else 0,
-                           dsrc=acts[i] if act else None, dsrc_view=_view(C) if act else None, transposed=True)
-                g, gv = gp, _view(C)
+        grads = _tower_backward(g, _view(TOWER_PITCH, 0, 2), acts, weights, act, N, H, W)
         if BACKWARD_TRACE is not None:
             BACKWARD_TRACE.append(("tower", 4, 40, 5))
         return (None, None, None, *grads)
+
+
+class RingTowerDrop(torch.autograd.Function):
+    """``RingTower`` with the reference's element-wise input dropout of the pose CNN (site 1 of csrc/dropout.hip) on the 80 tower
+    channels: ``forward(x, act, seed, p, *weights)``.  The fifth layer writes a compact ``[2B,H,W,40]`` map like layers 1..4 and
+    ``dl_tower_wide_drop_f32`` makes the wide stem input from it (both slices times the mask, channels 80..127 zero).  The un-dropped
+    map is kept: the stem must read dropped values, the tower's backward needs act' of the un-dropped ones (335 MB more than
+    ``RingTower`` at 64 x 2048, B = 8).  Backward: the incoming gradient is the TRUE ``dL/dxw`` (``RingStemWide`` with
+    ``dact_input = False``); ``dl_tower_wide_drop_bwd_f32`` regenerates the mask from the seed and returns layer 5's pre-activation
+    gradient in the compact layout, from which layers 5..1 run as in ``RingTower``."""
+
+    @staticmethod
+    def forward(ctx, x, act, seed, p, *weights):
+        B, _, H, W = x.shape
+        N = 2 * B
+        CH = TOWER_CHANNELS // 2
+        a = x.contiguous().view(N, 4, H, W).permute(0, 2, 3, 1).contiguous()
+        acts = [a]
+        ws = [weight_storage(w) for w in weights]
+        for i, (C, K) in enumerate(TOWER_PLAN):
+            y = _empty((N, H, W, K), torch.float32, x.device)
+            tower_conv(a, ws[i], y, (N, H, W, C, K), _view(C), _view(K), act=act, epilogue=EPI_ACT if act else 0)
+            acts.append(y)
+            a = y
+        xw = _empty((B, H, W, TOWER_PITCH), torch.float32, x.device)
+        _lib.check(_lib.load().dl_tower_wide_drop_f32(_ptr(a), _ptr(seed), float(p), B, H, W, CH, TOWER_PITCH, _ptr(xw), _stream()),
+                   "dl_tower_wide_drop_f32")
+        ctx.save_for_backward(*acts, seed, *weights)
+        ctx.act, ctx.p = act, float(p)
+        return xw
+
+    @staticmethod
+    def backward(ctx, gx):
+        saved = ctx.saved_tensors
+        acts, seed, weights = saved[:6], saved[6], saved[7:]
+        act = ctx.act
+        N, H, W, CH = acts[5].shape
+        gx = gx.contiguous()
+        g = _empty((N, H, W, CH), torch.float32, gx.device)
+        _lib.check(_lib.load().dl_tower_wide_drop_bwd_f32(_ptr(gx), _ptr(acts[5]), _ptr(seed), ctx.p, int(act), N // 2, H, W, CH, TOWER_PITCH, _ptr(g),
+                                                          _stream()), "dl_tower_wide_drop_bwd_f32")
+        grads = _tower_backward(g, _view(CH), acts, weights, act, N, H, W)
+        if BACKWARD_TRACE is not None:
+            BACKWARD_TRACE.append(("tower_drop", 4, 40, 5))
+        return (None, None, None, None, *grads)
 
 
 class RingStemWide(torch.autograd.Function):

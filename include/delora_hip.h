@@ -620,6 +620,34 @@ int dl_heads_bwd_drop(const float* x, const dl_heads_params* params, int32_t B, 
                       void* workspace, dl_stream stream);
 
 /*
+ * The single-MLP head (`use_single_mlp_at_output`; reference src/models/model.py:59-72, :106-114) on the same kernels' pattern: fc, then
+ * [act, Linear] five times down to 7 outputs; rotation = y[:, :4] / ||y[:, :4]||_F (ONE norm over the whole batch of raw quaternions),
+ * translation = y[:, 4:].  fp32, 1 <= B <= 16, act as above.  Layer l = 0..5 has w[l] [n_{l+1}][n_l] and b[l] [n_{l+1}] with the widths
+ * n = (F, R, H1, H2, H3, H4, 7); the reference's are (512, resnet_outputs, 512, 512, 256, 64, 7).  Any widths from 1 to 2^20 are
+ * served; the kernels are laid out for widths of a few thousand at most (the last layer and its backward are ONE workgroup whose
+ * threads walk H4 serially: correct, but slow for a very wide H4).
+ *   dl_heads_single_fwd  -> acts = the five activated layer outputs back to back, [B][R] | [B][H1] | [B][H2] | [B][H3] | [B][H4], the
+ *                           first one act((fc(x) + bias) * fc_scale) when fc_scale [B][R] is not NULL (the dropout mask of the fc output,
+ *                           dl_dropout_scale_f32 site 3); rot_raw [B][4], translation [B][3], rotation [B][4], norm [1].  Six launches.
+ *                           (acts, rot_raw, norm: saved for the backward)
+ *   dl_heads_single_bwd  -> the twelve parameter gradients (`grads`: same struct, writable buffers of the parameters' shapes) and grad_x
+ *                           [B][F]; fc_scale as in the forward or NULL; workspace: dl_heads_single_bwd_workspace_bytes (0 = sizes
+ *                           refused).  Eleven launches, fixed summation orders, no atomics.
+ */
+typedef struct {
+  const float* w[6];   /* fc, then the five Linear layers: [n_{l+1}][n_l] */
+  const float* b[6];   /* [n_{l+1}] */
+} dl_heads_single_params;
+int dl_heads_single_fwd(const float* x, const dl_heads_single_params* params, int32_t B, int32_t F, int32_t R, int32_t H1, int32_t H2,
+                        int32_t H3, int32_t H4, int32_t act, const float* fc_scale, float* acts, float* rot_raw, float* translation,
+                        float* rotation, float* norm, dl_stream stream);
+size_t dl_heads_single_bwd_workspace_bytes(int32_t B, int32_t F, int32_t R, int32_t H1, int32_t H2, int32_t H3, int32_t H4);
+int dl_heads_single_bwd(const float* x, const dl_heads_single_params* params, int32_t B, int32_t F, int32_t R, int32_t H1, int32_t H2,
+                        int32_t H3, int32_t H4, int32_t act, const float* fc_scale, const float* acts, const float* rot_raw,
+                        const float* norm, const float* grad_translation, const float* grad_rotation,
+                        const dl_heads_single_params* grads, float* grad_x, void* workspace, dl_stream stream);
+
+/*
  * Dropout of the pose CNN (csrc/dropout.hip; reference src/models/resnet_modified.py:33-38, :95-118: p = 0.2, training mode only).
  * The random stream is this library's own and has a contract a host program can replay:
  *   generator   Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85)
@@ -646,6 +674,20 @@ int dl_stem_input_nhwc_drop_f32(const float* x_nchw, int32_t N, int32_t C, int32
 int dl_channel_scale_nhwc_t(const void* x, const float* scale, int32_t N, int32_t P, int32_t C, int32_t dtype, void* y, dl_stream stream);
 int dl_channel_scale_bwd_act_nhwc_t(const void* g, const void* x, const float* scale, int32_t N, int32_t P, int32_t C, int32_t act,
                                     int32_t dtype, void* g_pre, dl_stream stream);
+
+/* Site 1 behind the feature tower (`use_dropout` with `pre_feature_extraction`; reference src/models/resnet_modified.py:95-97: the
+ * element-wise dropout hits the 80 concatenated tower channels).  Decision index i = ((b H + h) W + w) * 2 CH + c in the LOGICAL
+ * channels-last [B][H][W][2 CH] tensor, c < CH image 1's tower, c >= CH image 2's; the pitch does not enter.  CH % 4 == 0, pitch % 4 == 0,
+ * 2 CH <= pitch, B H W pitch < 2^31.
+ *   dl_tower_wide_drop_f32      y5 [2B][H][W][CH] (compact, UN-dropped layer-5 output, image n = 2 b + k) -> xw [B][H][W][pitch]:
+ *                               xw[b,h,w,k CH + c] = y5[n,h,w,c] * s(i); channels 2 CH .. pitch - 1 are written as zeros.
+ *   dl_tower_wide_drop_bwd_f32  gx [B][H][W][pitch] (the true dL/dxw; channels 2 CH .. are not read) ->
+ *                               g5[n,h,w,c] = (gx[b,h,w,k CH + c] * s(i)) * act'(y5[n,h,w,c]): the gradient of layer 5's pre-activation,
+ *                               the mask regenerated from the seed (no mask tensor exists). */
+int dl_tower_wide_drop_f32(const float* y5, const uint64_t* seed, double p, int32_t B, int32_t H, int32_t W, int32_t CH, int32_t pitch,
+                           float* xw, dl_stream stream);
+int dl_tower_wide_drop_bwd_f32(const float* gx, const float* y5, const uint64_t* seed, double p, int32_t act, int32_t B, int32_t H, int32_t W,
+                               int32_t CH, int32_t pitch, float* g5, dl_stream stream);
 
 /* Quaternion (x,y,z,w) + translation -> T [B][4][4] = [[R, t], [0, 1]] and its backward (reference src/models/model_parts.py:
  * 24-44; R = kornia 0.3.0 quaternion_to_rotation_matrix: normalise with eps, then the element-wise formula):
