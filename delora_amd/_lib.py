@@ -115,6 +115,12 @@ SIGNATURES = {
     "dl_conv2d_wgrad_batch_h_workspace_bytes": (_sz, [_vp, _i32]),
     "dl_conv2d_wgrad_batch_nhwc_h": (_i32, [_vp, _i32, _vp, _i32, _vp]),
     "dl_conv_plan_describe": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_char_p, _sz]),
+    "dl_pose_net_prepared_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "dl_pose_net_prepare": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "dl_pose_net_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "dl_pose_net_forward": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "dl_odometry_workspace_bytes": (_sz, [_vp, _SP, _i32, _i32, _i32]),
+    "dl_odometry_push": (_i32, [_vp, _vp, _SP, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dl_profile_begin": (_i32, [_i32, ctypes.c_char_p]),
     "dl_profile_end": (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "dl_profile_pause": (_i32, [_i32]),
@@ -137,6 +143,21 @@ class HeadsParams(ctypes.Structure):
 class HeadsSingleParams(ctypes.Structure):
     """``dl_heads_single_params`` of include/delora_hip.h (six weights, six biases: parameters, or buffers for their gradients)."""
     _fields_ = [("w", ctypes.c_void_p * 6), ("b", ctypes.c_void_p * 6)]
+
+
+POSE_NET_MAX_BLOCKS = 16
+
+
+class PoseBlock(ctypes.Structure):
+    """``dl_pose_block`` of include/delora_hip.h."""
+    _fields_ = [("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("stride_h", ctypes.c_int32), ("stride_w", ctypes.c_int32),
+                ("has_downsample", ctypes.c_int32), ("w1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("wd", ctypes.c_void_p)]
+
+
+class PoseNet(ctypes.Structure):
+    """``dl_pose_net`` of include/delora_hip.h."""
+    _fields_ = [("act", ctypes.c_int32), ("n_blocks", ctypes.c_int32), ("conv1_w", ctypes.c_void_p), ("blocks", PoseBlock * POSE_NET_MAX_BLOCKS),
+                ("heads", HeadsParams), ("F", ctypes.c_int32), ("R", ctypes.c_int32), ("Hd", ctypes.c_int32)]
 
 
 class ConvHLayer(ctypes.Structure):

@@ -1,0 +1,294 @@
+"""Inference through the C ABI alone: the pose network as ``dl_pose_net`` (include/delora_hip.h, csrc/infer.hip) and its weight file.
+
+``NativePoseNet`` binds an ``OdometryModel`` to ``dl_pose_net_prepare`` / ``dl_pose_net_forward``: the parameters are viewed in place
+(as ``ring_conv.weight_storage`` does), the Winograd-domain weights are produced once and the workspace is allocated once, so a
+forward pass is ONE library call that allocates nothing but its three small outputs.  torch is only the allocator here; a C or C++
+program does the same with ``hipMalloc`` (tools/odometry_demo.hip) from the file ``export_pose_net`` writes -- the counterpart of
+the reference's scripts/convert_pytorch_models.py, which re-saves a checkpoint for its inference node.
+
+Weight file (little-endian; INTEGRATION.md section C has the same description for non-Python readers):
+
+    bytes 0..7    magic  b"DLPOSNET"
+    bytes 8..11   uint32 format version (1)
+    bytes 12..15  uint32 n = length of the JSON header in bytes
+    bytes 16..    the JSON header (UTF-8), zero padding up to the next multiple of 256 = ``data_offset``
+    data_offset.. ``data_bytes`` bytes of raw fp32 arrays, each starting at a multiple of 256 relative to ``data_offset``
+
+    header = {"format": 1, "activation": "tanh" | "relu", "F": .., "R": .., "Hd": ..,
+              "blocks": [{"cin": .., "cout": .., "stride": [sh, sw], "has_downsample": true | false}, ...],
+              "sensor": {"H": .., "W": .., "hfov": [rad, rad], "vfov": [rad, rad]} | null,
+              "data_offset": .., "data_bytes": ..,
+              "arrays": {name: {"offset": bytes from data_offset, "shape": [...]}}}
+
+Array names and layouts (the C layouts of ``dl_pose_net``): ``conv1_w`` [64][3][3][8]; ``blocks.<i>.w1`` [cout][3][3][cin], ``blocks.<i>.w2``
+[cout][3][3][cout], ``blocks.<i>.wd`` [cout][1][1][cin]; ``heads.fc_w`` [R][F], ``heads.fc_b`` [R], ``heads.r1_w`` [Hd][R], ``heads.r1_b``,
+``heads.r3_w`` [4][Hd], ``heads.r3_b``, ``heads.t1_w`` [Hd][R], ``heads.t1_b``, ``heads.t3_w`` [3][Hd], ``heads.t3_b``.
+"""
+import ctypes
+import json
+import struct
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..models import ring_conv
+
+MAGIC = b"DLPOSNET"
+FORMAT_VERSION = 1
+ALIGN = 256
+MAX_BATCH = 16
+HEAD_NAMES = ("fc_w", "fc_b", "r1_w", "r1_b", "r3_w", "r3_b", "t1_w", "t1_b", "t3_w", "t3_b")
+
+
+def _align(n):
+    return (int(n) + ALIGN - 1) // ALIGN * ALIGN
+
+
+def why_unsupported(model, H, W, B=1):
+    """None when ``dl_pose_net`` serves this model on ``[B,8,H,W]`` inputs, else the reason (the C side's scope, restated on the
+    model's config so that a caller hears it before anything is built)."""
+    cfg = model.config
+    if cfg.get("pre_feature_extraction"):
+        return "pre_feature_extraction (the per-image feature tower) is not served by dl_pose_net"
+    if cfg.get("use_single_mlp_at_output"):
+        return "use_single_mlp_at_output is not served by dl_pose_net (two-MLP heads only)"
+    if not 1 <= int(B) <= MAX_BATCH:
+        return f"a batch of {B} is not served (1 <= B <= {MAX_BATCH})"
+    resnet = model.resnet
+    blocks, _ = resnet._trunk_blocks()
+    C0 = resnet.conv1.out_channels
+    if resnet.conv1.in_channels != 8 or C0 != 64 or any(cin % 64 or cout % 64 for (cin, cout, _, _) in blocks):
+        return "narrow networks (factor_fewer_resnet_channels > 1) are not served by dl_pose_net: channel counts must be multiples of 64"
+    if len(blocks) > _lib.POSE_NET_MAX_BLOCKS:
+        return f"{len(blocks)} residual blocks are not served (at most {_lib.POSE_NET_MAX_BLOCKS})"
+    if any(has_ds == (tuple(stride) == (1, 1)) or (not has_ds and cin != cout) for (cin, cout, stride, has_ds) in blocks):
+        return "a 1x1 shortcut on a stride-1 block (or none on a strided one) is not served by dl_pose_net"
+    if not ring_conv.stem_supported((B, 8, H, W), C0) or not ring_conv.supported((B, H, W // 4, C0), blocks):
+        return f"a {H}x{W} image is not served (a width that is a multiple of 4, activations below 2^31 elements)"
+    return None
+
+
+def _head_tensors(model):
+    fr, ft = model.fully_connected_rotation, model.fully_connected_translation
+    return (model.resnet.fc.weight, model.resnet.fc.bias, fr[1].weight, fr[1].bias, fr[3].weight, fr[3].bias, ft[1].weight, ft[1].bias,
+            ft[3].weight, ft[3].bias)
+
+
+def _arrays(model):
+    """name -> tensor in the C layout, views of the parameters wherever their memory already has that layout (conv1 keeps torch's default
+    layout and is re-laid out; the trunk's weights are views after ``trunk_weights_channels_last``)."""
+    out = {"conv1_w": ring_conv.weight_storage(model.resnet.conv1.weight.detach())}
+    blocks, weights = model.resnet._trunk_blocks()
+    wi = 0
+    for i, (_, _, _, has_ds) in enumerate(blocks):
+        out[f"blocks.{i}.w1"] = ring_conv.weight_storage(weights[wi].detach())
+        out[f"blocks.{i}.w2"] = ring_conv.weight_storage(weights[wi + 1].detach())
+        if has_ds:
+            out[f"blocks.{i}.wd"] = ring_conv.weight_storage(weights[wi + 2].detach())
+        wi += 3 if has_ds else 2
+    for name, t in zip(HEAD_NAMES, _head_tensors(model)):
+        out["heads." + name] = t.detach().contiguous()
+    return blocks, out
+
+
+def fill_pose_net(net, act, blocks, sizes, address):
+    """Fill a ``_lib.PoseNet``: act 1 / 2, blocks = (cin, cout, stride, has_downsample) tuples, sizes = (F, R, Hd), ``address(name)`` = the
+    device address of an array by its weight-file name."""
+    net.act, net.n_blocks = int(act), len(blocks)
+    net.conv1_w = address("conv1_w")
+    for i, (cin, cout, stride, has_ds) in enumerate(blocks):
+        b = net.blocks[i]
+        b.cin, b.cout, b.stride_h, b.stride_w, b.has_downsample = int(cin), int(cout), int(stride[0]), int(stride[1]), int(bool(has_ds))
+        b.w1, b.w2 = address(f"blocks.{i}.w1"), address(f"blocks.{i}.w2")
+        b.wd = address(f"blocks.{i}.wd") if has_ds else None
+    for name in HEAD_NAMES:
+        setattr(net.heads, name, address("heads." + name))
+    net.F, net.R, net.Hd = (int(v) for v in sizes)
+    return net
+
+
+class NativePoseNet(object):
+    """An ``OdometryModel`` behind ``dl_pose_net_forward`` for inputs ``[B,4,H,W]`` + ``[B,4,H,W]``.
+
+    The struct points INTO the model's parameters (conv1, whose parameter keeps torch's default layout, is the one copy): an in-place
+    weight update is seen by the stem, the strided and 1x1 layers and the heads at the next forward pass, and by the Winograd layers
+    after the next ``prepare()``.  ``prepared`` / ``workspace``: optional caller-owned fp32 / uint8 CUDA tensors of at least
+    ``prepared_bytes`` / ``workspace_bytes`` bytes, 256-byte aligned (tests carve them out of a poisoned arena)."""
+
+    def __init__(self, model, B, H, W, prepared=None, workspace=None, own_workspace=True):
+        why = why_unsupported(model, H, W, B)
+        if why is not None:
+            raise ValueError("NativePoseNet: " + why)
+        self.lib = _lib.load()
+        self.B, self.H, self.W = int(B), int(H), int(W)
+        self.device = model.resnet.conv1.weight.device
+        if self.device.type != "cuda":
+            raise _lib.DeloraHipError("NativePoseNet needs the model on the GPU (no CPU implementation)")
+        blocks, self._tensors = _arrays(model)                       # (kept: the struct holds raw addresses)
+        act = ring_conv.ACT["relu" if model.config["activation_fct"] == "relu" else "tanh"]
+        heads = _head_tensors(model)
+        self.net = fill_pose_net(_lib.PoseNet(), act, blocks, (heads[0].shape[1], heads[0].shape[0], heads[2].shape[0]),
+                                 lambda name: self._tensors[name].data_ptr())
+        self._net_p = ctypes.cast(ctypes.pointer(self.net), ctypes.c_void_p)
+        self.prepared_bytes = self._size("dl_pose_net_prepared_bytes")
+        self.workspace_bytes = self._size("dl_pose_net_workspace_bytes")
+        self.prepared = prepared if prepared is not None else torch.empty((self.prepared_bytes // 4,), dtype=torch.float32, device=self.device)
+        if workspace is None and own_workspace:
+            workspace = torch.empty((self.workspace_bytes,), dtype=torch.uint8, device=self.device)
+        self.workspace = workspace                                   # (None: ``forward`` is not used, the owner calls the library itself)
+        for name, t, need in (("prepared", self.prepared, self.prepared_bytes), ("workspace", self.workspace, self.workspace_bytes)):
+            if t is not None and (t.numel() * t.element_size() < need or not t.is_contiguous()):
+                raise ValueError(f"NativePoseNet: {name} needs {need} contiguous bytes")
+        self.prepare()
+
+    def _size(self, fn):
+        n = int(getattr(self.lib, fn)(self._net_p, self.B, self.H, self.W))
+        if not n:
+            raise _lib.DeloraHipError(f"{fn}: {(self.lib.dl_last_error() or b'').decode()}")
+        return n
+
+    @staticmethod
+    def supported(model, H, W, B=1):
+        return why_unsupported(model, H, W, B) is None
+
+    def prepare(self):
+        """The Winograd-domain weights of the stride-1 3x3 layers from the parameters as they are NOW (one launch)."""
+        _lib.check(self.lib.dl_pose_net_prepare(self._net_p, self.B, self.H, self.W, ring_conv._ptr(self.prepared), ring_conv._stream()),
+                   "dl_pose_net_prepare")
+
+    def forward(self, image_prev, image_cur, out=None):
+        """Two planar fp32 images ``[B,4,H,W]`` (dense inner dims, any scan stride) -> (translation [B,3], quaternion [B,4], T [B,4,4]);
+        ``out``: those three as caller-owned contiguous fp32 tensors (nothing is allocated then)."""
+        if self.workspace is None:
+            raise _lib.DeloraHipError("NativePoseNet was built without a workspace")
+        ptrs = []
+        for t in (image_prev, image_cur):
+            if (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (self.B, 4, self.H, self.W) or t.stride(3) != 1
+                    or t.stride(2) != self.W or t.stride(1) != self.H * self.W):
+                raise ValueError(f"expected planar fp32 CUDA [{self.B},4,{self.H},{self.W}] with dense inner dims, got {tuple(t.shape)} / {t.stride()}")
+            ptrs += [ring_conv._ptr(t), t.stride(0) if self.B > 1 else 4 * self.H * self.W]
+        if out is None:
+            out = tuple(torch.empty((self.B,) + s, dtype=torch.float32, device=self.device) for s in ((3,), (4,), (4, 4)))
+        translation, quaternion, T = out
+        for t, s in zip(out, ((3,), (4,), (4, 4))):
+            if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (self.B,) + s or not t.is_contiguous():
+                raise ValueError(f"out: expected contiguous fp32 CUDA {(self.B,) + s}, got {tuple(t.shape)}")
+        _lib.check(self.lib.dl_pose_net_forward(self._net_p, ring_conv._ptr(self.prepared), *ptrs, self.B, self.H, self.W, ring_conv._ptr(self.workspace),
+                                                ring_conv._ptr(translation), ring_conv._ptr(quaternion), ring_conv._ptr(T), ring_conv._stream()),
+                   "dl_pose_net_forward")
+        return translation, quaternion, T
+
+
+class NativeOdometry(object):
+    """``dl_odometry_push`` with its buffers: two ping-pong images, the offsets vector, the workspace (grown when a larger scan
+    arrives) and the three outputs.  ``push(points [3,N])`` returns None for the first scan, then (translation [1,3], quaternion [1,4],
+    T [1,4,4]) -- tensors that the next push overwrites.  ``image_t_1`` / ``image_t`` are the images of the last pair."""
+
+    def __init__(self, model, sensor, max_points=1 << 17):
+        self.pose = NativePoseNet(model, 1, sensor.H, sensor.W, own_workspace=False)     # (the forward's workspace is the head of this one's)
+        self.lib, self.sensor, dev = self.pose.lib, sensor, self.pose.device
+        self.images = torch.zeros((2, 4, sensor.H, sensor.W), dtype=torch.float32, device=dev)
+        self.offs = torch.zeros((2,), dtype=torch.int32, device=dev)
+        self.translation = torch.empty((1, 3), dtype=torch.float32, device=dev)
+        self.quaternion = torch.empty((1, 4), dtype=torch.float32, device=dev)
+        self.T = torch.empty((1, 4, 4), dtype=torch.float32, device=dev)
+        self.max_points, self.workspace = 0, None
+        self._reserve(max_points)
+        self.cur, self.count = 0, 0
+
+    def _reserve(self, n_points):
+        if self.workspace is not None and n_points <= self.max_points:
+            return
+        self.max_points = max(int(n_points), 2 * self.max_points)
+        nbytes = int(self.lib.dl_odometry_workspace_bytes(self.pose._net_p, ctypes.byref(self.sensor.struct), self.max_points, self.sensor.H, self.sensor.W))
+        if not nbytes:
+            raise _lib.DeloraHipError(f"dl_odometry_workspace_bytes: {(self.lib.dl_last_error() or b'').decode()}")
+        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=self.pose.device)
+
+    @property
+    def image_t(self):
+        return self.images[self.cur]
+
+    @property
+    def image_t_1(self):
+        return self.images[1 - self.cur]
+
+    def push(self, points):
+        if not points.is_cuda or points.dtype != torch.float32 or points.dim() != 2 or points.shape[0] < 3 or points.stride(1) != 1:
+            raise ValueError("points must be fp32 CUDA [>=3,N] with unit inner stride")
+        n = int(points.shape[1])
+        self._reserve(n)
+        if self.count:
+            self.cur = 1 - self.cur                                  # the swap of the two image buffers
+        prev = self.images[1 - self.cur] if self.count else None
+        p = ring_conv._ptr
+        _lib.check(self.lib.dl_odometry_push(self.pose._net_p, p(self.pose.prepared), ctypes.byref(self.sensor.struct), p(points), points.stride(0), n,
+                                             p(self.offs), p(prev), p(self.images[self.cur]), p(self.workspace), p(self.translation), p(self.quaternion),
+                                             p(self.T), ring_conv._stream()), "dl_odometry_push")
+        self.count += 1
+        return (self.translation, self.quaternion, self.T) if prev is not None else None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def export_pose_net(model, path, sensor=None):
+    """Write the model's weights as the flat file described at the top of this module; ``sensor``: a ``geometry.Sensor`` (or None).
+    Works for a model on any device.  Returns the header."""
+    why = why_unsupported(model, 4, 4)                               # (the smallest image: the file does not depend on the image size)
+    if why is not None:
+        raise ValueError("export_pose_net: " + why)
+    blocks, tensors = _arrays(model)
+    heads = _head_tensors(model)
+    arrays, off, blobs = {}, 0, []
+    for name, t in tensors.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy().astype("<f4", copy=False))
+        arrays[name] = {"offset": off, "shape": list(a.shape)}
+        blobs.append((off, a))
+        off = _align(off + a.nbytes)
+    header = {"format": FORMAT_VERSION, "activation": "relu" if model.config["activation_fct"] == "relu" else "tanh",
+              "F": int(heads[0].shape[1]), "R": int(heads[0].shape[0]), "Hd": int(heads[2].shape[0]),
+              "blocks": [{"cin": int(cin), "cout": int(cout), "stride": [int(s[0]), int(s[1])], "has_downsample": bool(ds)} for (cin, cout, s, ds) in blocks],
+              "sensor": None if sensor is None else {"H": sensor.H, "W": sensor.W, "hfov": list(sensor.hfov), "vfov": list(sensor.vfov)},
+              "data_offset": 0, "data_bytes": off, "arrays": arrays}
+    # the header names its own padded length: settle it with the widest plausible number, then pad the text to that length
+    header["data_offset"] = _align(16 + len(json.dumps(header).encode()) + 16)
+    text = json.dumps(header).encode()
+    with open(path, "wb") as f:
+        f.write(MAGIC + struct.pack("<II", FORMAT_VERSION, len(text)) + text)
+        f.write(b"\0" * (header["data_offset"] - 16 - len(text)))
+        pos = 0
+        for o, a in blobs:
+            f.write(b"\0" * (o - pos))
+            f.write(a.tobytes())
+            pos = o + a.nbytes
+        f.write(b"\0" * (off - pos))
+    return header
+
+
+def load_pose_net_blob(path):
+    """Read a weight file back: (header, {name: fp32 numpy array}).  A wrong magic, an unknown format version, a header that does not
+    parse and a file shorter than its header announces are ``ValueError``."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 16 or raw[:8] != MAGIC:
+        raise ValueError(f"{path}: not a pose-network weight file (magic {raw[:8]!r})")
+    version, n = struct.unpack("<II", raw[8:16])
+    if version != FORMAT_VERSION:
+        raise ValueError(f"{path}: format version {version}, this reader knows {FORMAT_VERSION}")
+    if len(raw) < 16 + n:
+        raise ValueError(f"{path}: truncated inside the header ({len(raw)} bytes, the header ends at {16 + n})")
+    try:
+        header = json.loads(raw[16:16 + n].decode())
+        base, nbytes = int(header["data_offset"]), int(header["data_bytes"])
+        entries = {name: (int(e["offset"]), tuple(int(d) for d in e["shape"])) for name, e in header["arrays"].items()}
+    except (ValueError, KeyError, TypeError) as e:
+        raise ValueError(f"{path}: the header does not parse: {e}") from e
+    if base < 16 + n or base % ALIGN or len(raw) < base + nbytes:
+        raise ValueError(f"{path}: truncated ({len(raw)} bytes, the header announces {base + nbytes})")
+    arrays = {}
+    for name, (off, shape) in entries.items():
+        count = int(np.prod(shape, dtype=np.int64))
+        if off % ALIGN or off < 0 or off + 4 * count > nbytes:
+            raise ValueError(f"{path}: array {name} lies outside the data section")
+        arrays[name] = np.frombuffer(raw, dtype="<f4", count=count, offset=base + off).reshape(shape).copy()
+    return header, arrays

@@ -99,9 +99,17 @@ class ScanToScanOdometry(object):
     config: the dict of ``bin/run_rosnode.py`` (the training config plus ``checkpoint``, ``datasets=[name]``,
     ``integrate_odometry``).  ``model`` / ``project_pair`` can be injected (tests run the core on the CPU with the
     oracle's projection); by default the model is built from the config and loaded from ``config["checkpoint"]`` and
-    the projection is the HIP one."""
+    the projection is the HIP one.
 
-    def __init__(self, config, model=None, project_pair=None):
+    ``engine``: "torch" (default) runs the model's modules on the stacked pair; "native" drives ``dl_odometry_push`` (the torch-free
+    C ABI of include/delora_hip.h, through ``deploy.native_infer.NativeOdometry``) with two ping-pong images -- the same kernels on the
+    same operands, so the same numbers, for the configs that path serves: the 8-channel full-width network with two-MLP heads and no
+    ``normalization_scaling``; anything else raises ``ValueError`` at construction."""
+
+    def __init__(self, config, model=None, project_pair=None, engine="torch"):
+        if engine not in ("torch", "native"):
+            raise ValueError(f"engine must be 'torch' or 'native', got {engine!r}")
+        self.engine = engine
         self.config = config
         self.device = config["device"]
         self.dataset = config["datasets"][0]                       # "Assumes the dataset in config['datasets'][0]" (:26)
@@ -117,6 +125,32 @@ class ScanToScanOdometry(object):
         self.integrator = TrajectoryIntegrator() if config.get("integrate_odometry", True) else None
         self.scaling_factor = 1.0
         self.point_cloud_t_1 = None
+        self.native = None
+        if engine == "native":
+            # scan -> pose through dl_odometry_push alone (include/delora_hip.h): only the new scan is projected, the Winograd-domain
+            # weights are prepared once, nothing is allocated per push
+            from ..deploy import native_infer
+            if project_pair is not None:
+                raise ValueError("engine 'native' projects inside the library: project_pair cannot be injected")
+            if config["normalization_scaling"]:
+                raise ValueError("engine 'native' does not serve normalization_scaling: it rescales both clouds per pair, so the previous "
+                                 "scan's image cannot be reused")
+            why = native_infer.why_unsupported(self.model, self.sensor.H, self.sensor.W)
+            if why is not None:
+                raise ValueError("engine 'native': " + why)
+            self.native = native_infer.NativeOdometry(self.model, self.sensor)
+
+    def _result(self, T, translation_1):
+        """The returned dict from ``T [1,4,4]`` and ``translation [1,3]`` (odometry_publisher.py:151-172)."""
+        quaternion = quaternion_from_matrix(T[0].double().cpu().numpy())
+        translation = translation_1[0].double().cpu().numpy() * self.scaling_factor
+        transformation = T[0].double().cpu().numpy().copy()
+        transformation[:3, 3] = translation
+        result = {"translation": translation, "quaternion": quaternion, "transformation": transformation}
+        if self.integrator is not None:
+            gt, gq = self.integrator.update_transformation(quaternion=quaternion, translation=translation)
+            result.update(global_translation=gt, global_quaternion=gq, T_0_t=self.integrator.T_0_t[0].copy())
+        return result
 
     def normalize_input(self, input_1, input_2):
         """Both clouds divided by the mean range over all their points, in place (odometry_publisher.py:104-113)."""
@@ -135,6 +169,9 @@ class ScanToScanOdometry(object):
             scan = torch.from_numpy(filter_scans(np.asarray(scan, dtype=np.float32)))
         current = scan[:, :3].to(self.device).float().clone()
         result = None
+        if self.native is not None:
+            out = self.native.push(current[0].contiguous())          # (a filtered numpy scan arrives with transposed strides)
+            return None if out is None else self._result(out[2], out[0])
         if self.point_cloud_t_1 is not None:
             previous = self.point_cloud_t_1
             if self.config["normalization_scaling"]:

@@ -1,6 +1,8 @@
 /*
- * delora_hip.h -- C ABI of libdelora_hip.so: the MI355X (gfx950) geometry kernels of the DeLORA
- * per-scan-pair training step.
+ * delora_hip.h -- C ABI of libdelora_hip.so: the MI355X (gfx950) kernels of DeLORA -- the geometry of the
+ * per-scan-pair training step (projection, normals, exact search, losses), the pose CNN's convolutions,
+ * pooling and heads, and on top of them the torch-free inference path scan -> pose (dl_pose_net_*,
+ * dl_odometry_push).
  *
  * The reference (leggedrobotics/delora) has no native layer; its boundary for this path is the
  * Python module API.  Each entry point below replaces the torch-op sequence of one reference
@@ -33,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), the narrow convolution family dl_tower_* (purely additive: the number stays), dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
+#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), the narrow convolution family dl_tower_* (purely additive: the number stays), dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays), inference without Python: dl_pose_net_* / dl_odometry_* (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
 
 typedef void* dl_stream;
 
@@ -700,6 +702,77 @@ int dl_quat_to_T_bwd(const float* quaternion, const float* grad_T, int32_t B, fl
 /* Global average pooling of a channels-last feature map (reference resnet_modified.py: avgpool + flatten before fc):
  * x [N][P][C] (P = H*W pixels) -> y [N][C]; fixed summation order; C % 4 == 0. */
 int dl_mean_hw_nhwc_f32(const float* x, int32_t N, int32_t P, int32_t C, float* y, dl_stream stream);
+
+/*
+ * INFERENCE WITHOUT PYTHON (csrc/infer.hip; additive, ABI 10 as it stands): scan -> pose on the entry points above, for a C or C++ caller that has no torch.
+ * Replaces the layer walk of the reference's inference node (src/ros_utils/odometry_publisher.py:104-172: project both scans, stack,
+ * model forward, quaternion -> T; bin/run_rosnode.py) and is what delora_amd/models/ring_conv.py (RingStem, RingSegment.forward) and
+ * model_parts.FusedHeads do in eval mode -- the SAME launches with the same operands in the same order, hence the same bits.
+ *
+ * dl_pose_net describes the network as the reference builds it (src/models/resnet_modified.py, src/models/model.py:74-83); every
+ * pointer is a DEVICE pointer to the RAW fp32 parameter, 16-byte aligned, in the layout the matching entry point takes:
+ *   conv1_w            [64][3][3][8]   (dl_conv2d_nhwc_f32; the torch parameter [64,8,3,3] in channels_last memory format)
+ *   blocks[i].w1 / w2  [cout][3][3][cin] / [cout][3][3][cout];  blocks[i].wd [cout][1][1][cin] when has_downsample, else NULL
+ *   heads              dl_heads_params for fc [R][F] and the two heads ([Hd][R], [4][Hd], [3][Hd]);  F = the last block's cout
+ * Scope: fp32, 8 input channels (two planar 4-channel range images), full-width channel counts (multiples of 64, the first block
+ * reading conv1's 64), strides (1,1), (1,2) or (2,2) with has_downsample exactly on the strided blocks (and cin == cout on the
+ * others), act 1 (tanh) or 2 (relu), the two-MLP heads, 1 <= B <= 16, H >= 1, W a multiple of 4, every activation below 2^31 elements.
+ * Anything else is DL_ERR_UNSUPPORTED with a text that names the offending field; null or misaligned pointers and non-positive sizes
+ * are DL_ERR_INVALID_ARGUMENT.  Everything is refused before any launch, through dl_last_error, the text naming the entry point.
+ *
+ * PREPARED WEIGHTS.  Every stride-1 3x3 layer runs as fused Winograd (dl_wino_conv3x3_nhwc_f32); its Winograd-domain forward weights
+ * are produced ONCE by dl_pose_net_prepare (dl_wino_weights_batch_f32, no backward weights) into the caller's `prepared` buffer of
+ * dl_pose_net_prepared_bytes bytes (the sum of dl_wino_weights_floats over those layers, in block order; 256-byte aligned) and stay
+ * valid until a weight changes.  A forward pass with stale prepared weights runs the Winograd layers on the OLD weights and the
+ * strided / 1x1 / stem / head layers, which read the raw parameters, on the new ones: prepare again after every weight update.
+ *
+ * FORWARD.  dl_pose_net_forward(image_prev, image_cur) enqueues: the input interleave (two planar [B][4][H][W] images with element
+ * scan strides prev_ss / cur_ss >= 4*H*W, channel stride H*W -> [B][H][W][8], channels 0..3 = image_prev: a bit copy, what
+ * torch.cat(dim=1).permute(0,2,3,1).contiguous() does), conv1 + activation, the pooling, per block conv (+ activation), the 1x1
+ * shortcut, conv (+ shortcut + activation), dl_mean_hw_nhwc_f32, dl_heads_fwd and dl_quat_to_T_fwd with eps 1e-12.
+ *   translation [B][3], quaternion [B][4] (x,y,z,w; divided by the norm over the whole batch, as the reference's model.py:114),
+ *   T [B][4][4] out.  workspace: dl_pose_net_workspace_bytes bytes, 256-byte aligned, need not be initialised: four rotating
+ *   activation slots (a block's input, y1, shortcut and y2; the stem's interleaved input, conv1 output and pooled map use the same
+ *   slots first), the pooling's int8 window plane, the largest split-K scratch of dl_wino_conv3x3_workspace_bytes, the pooled
+ *   feature and the heads' saved activations -- each carved at a 256-byte boundary.  Both size functions are host arithmetic (no GPU
+ *   needed) and return 0 with a text in dl_last_error for a refused net or shape.
+ *
+ * STREAMING ODOMETRY.  dl_odometry_push projects ONLY the new scan (dl_project, S = 1: pts [3][pts_cs] planar fp32, n_points columns
+ * in use) into image_cur [4][H][W] and runs the forward on (image_prev, image_cur) with B = 1; the caller swaps the two image
+ * buffers between calls, the library keeps no state.  image_prev == NULL only projects (the first scan; translation, quaternion and T
+ * may then be NULL and are not written).  offs is a caller-owned int32 [2] device vector the call overwrites (the CSR offsets {0,
+ * n_points}, written by a kernel on `stream`).  workspace: dl_odometry_workspace_bytes(net, sensor, max_points, H, W) bytes, 256-byte
+ * aligned, H and W being the sensor's; every push needs 0 <= n_points <= max_points (the projection's staging records are the tail of
+ * the workspace).  The reference's normalization_scaling rescales both clouds per pair and is not served: the previous image could
+ * not be reused.
+ */
+#define DL_POSE_ACT_TANH 1
+#define DL_POSE_ACT_RELU 2
+#define DL_POSE_NET_MAX_BLOCKS 16
+typedef struct {
+  int32_t cin, cout;             /* channels of the block's input / of its two convolutions' outputs */
+  int32_t stride_h, stride_w;    /* stride of the first convolution and of the shortcut */
+  int32_t has_downsample;        /* 1: the shortcut is the strided 1x1 convolution wd */
+  const float *w1, *w2, *wd;
+} dl_pose_block;
+typedef struct {
+  int32_t act;                   /* DL_POSE_ACT_TANH / DL_POSE_ACT_RELU (config activation_fct) */
+  int32_t n_blocks;              /* 1..DL_POSE_NET_MAX_BLOCKS (the reference: 8) */
+  const float* conv1_w;
+  dl_pose_block blocks[DL_POSE_NET_MAX_BLOCKS];
+  dl_heads_params heads;
+  int32_t F, R, Hd;              /* pooled feature width, resnet_outputs, hidden width of the heads (the reference: 512, 1000, 100) */
+} dl_pose_net;
+size_t dl_pose_net_prepared_bytes(const dl_pose_net* net, int32_t B, int32_t H, int32_t W);
+int dl_pose_net_prepare(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, void* prepared, dl_stream stream);
+size_t dl_pose_net_workspace_bytes(const dl_pose_net* net, int32_t B, int32_t H, int32_t W);
+int dl_pose_net_forward(const dl_pose_net* net, const void* prepared, const float* image_prev, int64_t prev_ss, const float* image_cur,
+                        int64_t cur_ss, int32_t B, int32_t H, int32_t W, void* workspace, float* translation, float* quaternion, float* T,
+                        dl_stream stream);
+size_t dl_odometry_workspace_bytes(const dl_pose_net* net, const dl_sensor* sensor, int32_t max_points, int32_t H, int32_t W);
+int dl_odometry_push(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs,
+                     int32_t n_points, int32_t* offs, const float* image_prev, float* image_cur, void* workspace, float* translation,
+                     float* quaternion, float* T, dl_stream stream);
 
 /*
  * What the convolution dispatch would launch (for tests and tools; host only, nothing is enqueued): runs the matching entry point's

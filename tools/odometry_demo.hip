@@ -1,0 +1,285 @@
+// Scan-to-scan odometry with no Python in it: a weight file written by delora_amd.deploy.native_infer.export_pose_net and a list of
+// raw scans (float32 [3][N]: all x, all y, all z) go through dl_pose_net_prepare (once) and dl_odometry_push (once per scan), exactly
+// as INTEGRATION.md section C describes for a C or C++ caller.  The counterpart of the reference's inference node (bin/run_rosnode.py)
+// without ROS.
+//
+//   odometry_demo <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...
+//
+// One line per pair of consecutive scans:   <index> T <16 x 8 hex digits> pose <12 numbers>
+// T = the fp32 bit patterns of the row-major 4x4 transform (previous -> current), pose = the first three rows of the accumulated
+// T_0_t (the KITTI odometry format), accumulated in double.  Every HIP and dl_* status is checked; the first failure ends the
+// program with a non-zero exit code.
+#include <hip/hip_runtime.h>
+
+#include <cctype>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
+
+// the library's sources, as the other stand-alone programs of this directory take them
+#include "../delora_amd/csrc/abi.hip"
+#include "../delora_amd/csrc/project.hip"
+#include "../delora_amd/csrc/conv.hip"
+#include "../delora_amd/csrc/wino.hip"
+#include "../delora_amd/csrc/stem.hip"
+#include "../delora_amd/csrc/pose.hip"
+#include "../delora_amd/csrc/heads.hip"
+#include "../delora_amd/csrc/infer.hip"
+
+#define HIP_OK(call)                                                                                         \
+  do {                                                                                                       \
+    const hipError_t e_ = (call);                                                                            \
+    if (e_ != hipSuccess) { fprintf(stderr, "odometry_demo: %s: %s\n", #call, hipGetErrorString(e_)); exit(2); } \
+  } while (0)
+#define DL_OK_OR_DIE(call)                                                                                   \
+  do {                                                                                                       \
+    const int rc_ = (call);                                                                                  \
+    if (rc_ != 0) { fprintf(stderr, "odometry_demo: %s -> %d: %s\n", #call, rc_, dl_last_error()); exit(3); } \
+  } while (0)
+
+static void die(const std::string& what) {
+  fprintf(stderr, "odometry_demo: %s\n", what.c_str());
+  exit(1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The JSON of the weight file's header: objects, arrays, strings without escapes beyond \" and \\, numbers, true / false / null.
+struct Json {
+  enum Kind { Null, Bool, Number, String, Array, Object } kind = Null;
+  bool b = false;
+  double num = 0.0;
+  std::string str;
+  std::vector<Json> items;
+  std::map<std::string, Json> fields;
+  const Json& at(const std::string& key) const {
+    auto it = fields.find(key);
+    if (kind != Object || it == fields.end()) die("weight file header: no field \"" + key + "\"");
+    return it->second;
+  }
+  const Json& at(size_t i) const {
+    if (kind != Array || i >= items.size()) die("weight file header: array too short");
+    return items[i];
+  }
+  long long integer() const {
+    if (kind != Number) die("weight file header: a number was expected");
+    return (long long)num;
+  }
+};
+
+struct JsonReader {
+  const char* p;
+  const char* end;
+  void skip() { while (p < end && isspace((unsigned char)*p)) ++p; }
+  void expect(char c) {
+    skip();
+    if (p >= end || *p != c) die(std::string("weight file header: '") + c + "' expected");
+    ++p;
+  }
+  std::string string() {
+    expect('"');
+    std::string s;
+    while (p < end && *p != '"') {
+      if (*p == '\\' && p + 1 < end) ++p;
+      s += *p++;
+    }
+    if (p >= end) die("weight file header: unterminated string");
+    ++p;
+    return s;
+  }
+  Json value() {
+    skip();
+    if (p >= end) die("weight file header: ends early");
+    Json v;
+    if (*p == '{') {
+      v.kind = Json::Object;
+      ++p; skip();
+      if (p < end && *p == '}') { ++p; return v; }
+      for (;;) {
+        skip();
+        const std::string key = string();
+        expect(':');
+        v.fields[key] = value();
+        skip();
+        if (p < end && *p == ',') { ++p; continue; }
+        expect('}');
+        return v;
+      }
+    }
+    if (*p == '[') {
+      v.kind = Json::Array;
+      ++p; skip();
+      if (p < end && *p == ']') { ++p; return v; }
+      for (;;) {
+        v.items.push_back(value());
+        skip();
+        if (p < end && *p == ',') { ++p; continue; }
+        expect(']');
+        return v;
+      }
+    }
+    if (*p == '"') { v.kind = Json::String; v.str = string(); return v; }
+    if (end - p >= 4 && !strncmp(p, "true", 4)) { v.kind = Json::Bool; v.b = true; p += 4; return v; }
+    if (end - p >= 5 && !strncmp(p, "false", 5)) { v.kind = Json::Bool; p += 5; return v; }
+    if (end - p >= 4 && !strncmp(p, "null", 4)) { p += 4; return v; }
+    char* after = nullptr;
+    const std::string text(p, (size_t)(end - p) < 64 ? (size_t)(end - p) : 64);
+    v.num = strtod(text.c_str(), &after);
+    if (after == text.c_str()) die("weight file header: a value was expected");
+    v.kind = Json::Number;
+    p += after - text.c_str();
+    return v;
+  }
+};
+
+static std::vector<char> read_file(const char* path) {
+  FILE* f = fopen(path, "rb");
+  if (!f) die(std::string("cannot open ") + path);
+  fseek(f, 0, SEEK_END);
+  const long n = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  std::vector<char> data((size_t)(n > 0 ? n : 0));
+  if (n > 0 && fread(data.data(), 1, (size_t)n, f) != (size_t)n) die(std::string("cannot read ") + path);
+  fclose(f);
+  return data;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 5) die("usage: odometry_demo <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...   (scans: float32 [3][N])");
+  // ---- the weight file
+  const std::vector<char> blob = read_file(argv[1]);
+  if (blob.size() < 16 || memcmp(blob.data(), "DLPOSNET", 8)) die("the weight file has a wrong magic");
+  uint32_t version, header_len;
+  memcpy(&version, blob.data() + 8, 4);
+  memcpy(&header_len, blob.data() + 12, 4);
+  if (version != 1) die("the weight file has format version " + std::to_string(version) + ", this program reads 1");
+  if (blob.size() < 16 + (size_t)header_len) die("the weight file is truncated inside its header");
+  JsonReader reader{blob.data() + 16, blob.data() + 16 + header_len};
+  const Json header = reader.value();
+  const size_t data_offset = (size_t)header.at("data_offset").integer(), data_bytes = (size_t)header.at("data_bytes").integer();
+  if (data_offset < 16 + (size_t)header_len || blob.size() < data_offset + data_bytes) die("the weight file is truncated");
+  if (header.at("sensor").kind != Json::Object) die("the weight file names no sensor");
+  const Json& sj = header.at("sensor");
+  dl_sensor sensor;
+  sensor.H = (int32_t)sj.at("H").integer(); sensor.W = (int32_t)sj.at("W").integer();
+  sensor.hfov0 = sj.at("hfov").at(0).num; sensor.hfov1 = sj.at("hfov").at(1).num;
+  sensor.vfov0 = sj.at("vfov").at(0).num; sensor.vfov1 = sj.at("vfov").at(1).num;
+  if (sensor.H < 2 || sensor.W < 2 || sensor.H > (1 << 14) || sensor.W > (1 << 16)) die("the weight file's sensor has an implausible size");
+  const int H = sensor.H, W = sensor.W;
+
+  // one device buffer for the whole data section: the arrays keep their 256-byte aligned offsets
+  char* d_weights = nullptr;
+  HIP_OK(hipMalloc((void**)&d_weights, data_bytes ? data_bytes : 256));
+  HIP_OK(hipMemcpy(d_weights, blob.data() + data_offset, data_bytes, hipMemcpyHostToDevice));
+  const Json& arrays = header.at("arrays");
+  auto address = [&](const std::string& name, size_t floats) -> const float* {
+    const Json& e = arrays.at(name);
+    const size_t off = (size_t)e.at("offset").integer();
+    size_t count = 1;
+    for (const Json& d : e.at("shape").items) count *= (size_t)d.integer();
+    if (count != floats) die("array " + name + " has " + std::to_string(count) + " elements, the header's sizes ask for " + std::to_string(floats));
+    if (off % 256 || off + 4 * count > data_bytes) die("array " + name + " lies outside the data section");
+    return (const float*)(d_weights + off);
+  };
+  // (the struct is large: it lives on the heap)
+  std::unique_ptr<dl_pose_net> net_holder(new dl_pose_net);
+  dl_pose_net& net = *net_holder;
+  memset(&net, 0, sizeof(net));
+  const std::string act = header.at("activation").str;
+  net.act = act == "relu" ? DL_POSE_ACT_RELU : act == "tanh" ? DL_POSE_ACT_TANH : 0;
+  const Json& blocks = header.at("blocks");
+  if (blocks.kind != Json::Array || blocks.items.empty() || blocks.items.size() > DL_POSE_NET_MAX_BLOCKS) die("the weight file has a bad number of blocks");
+  net.n_blocks = (int32_t)blocks.items.size();
+  net.F = (int32_t)header.at("F").integer(); net.R = (int32_t)header.at("R").integer(); net.Hd = (int32_t)header.at("Hd").integer();
+  if (net.F < 1 || net.R < 1 || net.Hd < 1) die("the weight file has bad head sizes");
+  net.conv1_w = address("conv1_w", 64 * 3 * 3 * 8);
+  for (int i = 0; i < net.n_blocks; ++i) {
+    const Json& bj = blocks.at((size_t)i);
+    dl_pose_block& b = net.blocks[i];
+    b.cin = (int32_t)bj.at("cin").integer(); b.cout = (int32_t)bj.at("cout").integer();
+    b.stride_h = (int32_t)bj.at("stride").at(0).integer(); b.stride_w = (int32_t)bj.at("stride").at(1).integer();
+    b.has_downsample = bj.at("has_downsample").b ? 1 : 0;
+    if (b.cin < 1 || b.cout < 1 || b.cin > (1 << 14) || b.cout > (1 << 14)) die("the weight file has bad channel counts");
+    const std::string base = "blocks." + std::to_string(i) + ".";
+    b.w1 = address(base + "w1", (size_t)b.cout * 9 * b.cin);
+    b.w2 = address(base + "w2", (size_t)b.cout * 9 * b.cout);
+    b.wd = b.has_downsample ? address(base + "wd", (size_t)b.cout * b.cin) : nullptr;
+  }
+  const size_t F = (size_t)net.F, R = (size_t)net.R, Hd = (size_t)net.Hd;
+  net.heads.fc_w = address("heads.fc_w", R * F); net.heads.fc_b = address("heads.fc_b", R);
+  net.heads.r1_w = address("heads.r1_w", Hd * R); net.heads.r1_b = address("heads.r1_b", Hd);
+  net.heads.r3_w = address("heads.r3_w", 4 * Hd); net.heads.r3_b = address("heads.r3_b", 4);
+  net.heads.t1_w = address("heads.t1_w", Hd * R); net.heads.t1_b = address("heads.t1_b", Hd);
+  net.heads.t3_w = address("heads.t3_w", 3 * Hd); net.heads.t3_b = address("heads.t3_b", 3);
+
+  // ---- the scans (read first: the largest one sizes the workspace)
+  std::vector<std::vector<char>> scans;
+  size_t max_points = 0;
+  for (int i = 3; i < argc; ++i) {
+    scans.push_back(read_file(argv[i]));
+    if (scans.back().size() % 12) die(std::string(argv[i]) + " is not a float32 [3][N] file");
+    if (scans.back().size() / 12 > ((size_t)1 << 30)) die(std::string(argv[i]) + " is too large");
+    if (scans.back().size() / 12 > max_points) max_points = scans.back().size() / 12;
+  }
+
+  // ---- buffers: all owned here, the library allocates nothing
+  const size_t prepared_bytes = dl_pose_net_prepared_bytes(&net, 1, H, W);
+  if (!prepared_bytes) die(std::string("dl_pose_net_prepared_bytes: ") + dl_last_error());
+  const size_t ws_bytes = dl_odometry_workspace_bytes(&net, &sensor, (int32_t)max_points, H, W);
+  if (!ws_bytes) die(std::string("dl_odometry_workspace_bytes: ") + dl_last_error());
+  void *prepared = nullptr, *workspace = nullptr;
+  float *images[2] = {nullptr, nullptr}, *d_pts = nullptr, *d_out = nullptr;
+  int32_t* d_offs = nullptr;
+  HIP_OK(hipMalloc(&prepared, prepared_bytes));
+  HIP_OK(hipMalloc(&workspace, ws_bytes));
+  HIP_OK(hipMalloc((void**)&images[0], (size_t)4 * H * W * 4));
+  HIP_OK(hipMalloc((void**)&images[1], (size_t)4 * H * W * 4));
+  HIP_OK(hipMalloc((void**)&d_pts, max_points ? max_points * 12 : 256));
+  HIP_OK(hipMalloc((void**)&d_offs, 256));
+  HIP_OK(hipMalloc((void**)&d_out, 256));                              // translation [3] | quaternion [4] | T [16] at floats 0, 4, 8
+  hipStream_t stream;
+  HIP_OK(hipStreamCreate(&stream));
+  DL_OK_OR_DIE(dl_pose_net_prepare(&net, 1, H, W, prepared, stream));
+
+  FILE* out = fopen(argv[2], "w");
+  if (!out) die(std::string("cannot write ") + argv[2]);
+  double pose[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+  int cur = 0;
+  for (size_t i = 0; i < scans.size(); ++i) {
+    const size_t n = scans[i].size() / 12;
+    if (n) HIP_OK(hipMemcpyAsync(d_pts, scans[i].data(), n * 12, hipMemcpyHostToDevice, stream));
+    if (i) cur = 1 - cur;                                            // the caller's swap of the two image buffers
+    DL_OK_OR_DIE(dl_odometry_push(&net, prepared, &sensor, d_pts, (int64_t)n, (int32_t)n, d_offs, i ? images[1 - cur] : nullptr, images[cur], workspace,
+                                  d_out, d_out + 4, d_out + 8, stream));
+    float T[16];
+    if (i) HIP_OK(hipMemcpyAsync(T, d_out + 8, sizeof(T), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));                            // (also: the scan buffer is free for the next copy)
+    if (!i) continue;
+    double next[4][4];
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) {
+        double s = 0.0;
+        for (int k = 0; k < 4; ++k) s += pose[r][k] * (double)T[4 * k + c];
+        next[r][c] = s;
+      }
+    memcpy(pose, next, sizeof(pose));
+    fprintf(out, "%zu T", i);
+    for (int k = 0; k < 16; ++k) {
+      uint32_t bits;
+      memcpy(&bits, &T[k], 4);
+      fprintf(out, " %08x", bits);
+    }
+    fprintf(out, " pose");
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 4; ++c) fprintf(out, " %.9e", pose[r][c]);
+    fprintf(out, "\n");
+  }
+  if (fclose(out)) die(std::string("cannot finish ") + argv[2]);
+  HIP_OK(hipStreamDestroy(stream));
+  for (void* p : {(void*)d_weights, prepared, workspace, (void*)images[0], (void*)images[1], (void*)d_pts, (void*)d_offs, (void*)d_out}) HIP_OK(hipFree(p));
+  printf("odometry_demo: %zu scans, %zu poses -> %s\n", scans.size(), scans.empty() ? (size_t)0 : scans.size() - 1, argv[2]);
+  return 0;
+}
