@@ -242,6 +242,51 @@ def wino_conv(x, u, K, act=0, epilogue=0, add=None, dsrc=None):
 
 _WINO_WS_BYTES = {}
 
+USE_WINOGRAD_STRIDED = True  # stride-(1,2) 3x3 layers on the Winograd kernel through the pixel-pair view (honoured only with USE_WINOGRAD)
+STRIDED_PLAN_CUS = 0         # CU count the plan query is asked with (0: the device's own)
+_STRIDED_TAKES = {}
+
+
+def wino_strided_ok(N, H, W, C, K, stride):
+    """Whether the dispatch runs a strided 3x3 layer (input ``[N,H,W,C]``) as pixel-pair Winograd: ``dl_wino_strided_takes``."""
+    key = (N, H, W, C, K, tuple(stride), STRIDED_PLAN_CUS)
+    ok = _STRIDED_TAKES.get(key)
+    if ok is None:
+        ok = _STRIDED_TAKES[key] = bool(_lib.load().dl_wino_strided_takes(N, H, W, C, K, stride[0], stride[1], STRIDED_PLAN_CUS))
+    return ok
+
+
+def wino_strided_weights(w_param, stride, want_bwd=True):
+    """(u_fwd, u_bwd) of a strided 3x3 layer's rearranged kernel (csrc/wino.hip: k_wino_weights_strided) from the parameter ``[K,C,3,3]``."""
+    lib = _lib.load()
+    w = weight_storage(w_param)
+    K, C = w.shape[0], w.shape[3]
+    n = int(lib.dl_wino_strided_weights_floats(K, C, stride[0], stride[1]))
+    uf = torch.empty((n,), dtype=torch.float32, device=w.device)
+    ub = torch.empty((n,), dtype=torch.float32, device=w.device) if want_bwd else None
+    _lib.check(lib.dl_wino_strided_weights_f32(_ptr(w), _ptr(uf), _ptr(ub), K, C, stride[0], stride[1], _stream()), "dl_wino_strided_weights_f32")
+    return uf, ub
+
+
+def wino_strided_conv(x, u_fwd, K, stride, act=0, epilogue=0):
+    """Strided 3x3 convolution of x ``[N,H,W,C]`` with the weights of ``wino_strided_weights`` -> ``[N,H/sh,W/sw,K]``."""
+    N, H, W, C = x.shape
+    y = _empty((N, H // stride[0], W // stride[1], K), torch.float32, x.device)
+    _lib.check(_lib.load().dl_wino_strided_conv3x3_nhwc_f32(_ptr(x), _ptr(u_fwd), _ptr(y), N, H, W, C, K, stride[0], stride[1], int(act),
+                                                           int(epilogue), _stream()), "dl_wino_strided_conv3x3_nhwc_f32")
+    return y
+
+
+def wino_strided_dgrad(g, u_bwd, C, stride, in_hw, act=0, epilogue=0, add_grid=None, dsrc=None):
+    """Input gradient ``[N,H,W,C]`` of the same layer from g ``[N,H/sh,W/sw,K]``; epilogue as ``dgrad_strided``."""
+    N, Ho, Wo, K = g.shape
+    H, W = int(in_hw[0]), int(in_hw[1])
+    assert Ho * stride[0] == H and Wo * stride[1] == W, (g.shape, in_hw, stride)
+    dx = _empty((N, H, W, C), torch.float32, g.device)
+    _lib.check(_lib.load().dl_wino_strided_dgrad3x3_nhwc_f32(_ptr(g), _ptr(u_bwd), _ptr(dx), _ptr(add_grid), _ptr(dsrc), N, H, W, K, C, stride[0],
+                                                            stride[1], int(act), int(epilogue), _stream()), "dl_wino_strided_dgrad3x3_nhwc_f32")
+    return dx
+
 
 def supported(x_shape, blocks):
     """Whether the HIP trunk can run these shapes: channel counts multiples of 64.  The image size is free: tiles hang over the edge
@@ -778,8 +823,9 @@ class RingSegment(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, act, blocks, first, last, *weights):
         """Stride-1 3x3 layers run as fused Winograd F(2x2,3x3) when ``USE_WINOGRAD`` and the shape tiles (their
-        Winograd-domain weights for the backward pass are produced by the same launch and kept for it); the strided and 1x1
-        layers run the direct kernel."""
+        Winograd-domain weights for the backward pass are produced by the same launch and kept for it); stride-(1,2) 3x3 layers
+        that ``dl_wino_strided_takes`` accepts run on the same kernel through the pixel-pair view (``USE_WINOGRAD_STRIDED``); the
+        other strided layers and the 1x1 layers run the direct kernel."""
         saved, x, wi = [x0], x0, 0
         ubwd = []
         need_bwd = any(ctx.needs_input_grad)
@@ -787,12 +833,14 @@ class RingSegment(torch.autograd.Function):
         plan, (N, H, W) = [], x0.shape[:3]
         for (cin, cout, stride, has_ds) in blocks:
             use1 = USE_WINOGRAD and stride == (1, 1) and wino_ok(H, W, cin, cout)
+            if USE_WINOGRAD and USE_WINOGRAD_STRIDED and tuple(stride) != (1, 1) and has_ds and wino_strided_ok(N, H, W, cin, cout, stride):
+                use1 = "strided"
             H, W = out_size(H, stride[0]), out_size(W, stride[1])
             use2 = USE_WINOGRAD and wino_ok(H, W, cout, cout)
             plan.append((use1, use2))
         wlist, wj = [], 0
         for (cin, cout, stride, has_ds), (use1, use2) in zip(blocks, plan):
-            if use1:
+            if use1 is True:
                 wlist.append(weights[wj])
             if use2:
                 wlist.append(weights[wj + 1])
@@ -802,7 +850,10 @@ class RingSegment(torch.autograd.Function):
             w1p, w2p = weights[wi], weights[wi + 1]
             wd = weight_storage(weights[wi + 2]) if has_ds else None
             wi += 3 if has_ds else 2
-            if use1:
+            if use1 == "strided":                            # the rearranged kernel's transform: one launch more per strided layer
+                uf, ub1 = wino_strided_weights(w1p, stride, want_bwd=need_bwd)
+                y1 = wino_strided_conv(x, uf, cout, stride, act=act, epilogue=EPI_ACT)
+            elif use1:
                 uf, ub1 = next(us)
                 y1 = wino_conv(x, uf, cout, act=act, epilogue=EPI_ACT)
             else:
@@ -877,7 +928,10 @@ class RingSegment(torch.autograd.Function):
                 # down-sampling branch on the grid, then one pass per stride phase of the 3x3 layer with it and act'(x) fused
                 dxb = dgrad_strided(g2, weight_storage(wdp), stride, x.shape[1:3], dense=True)
                 epi = EPI_ADD_GRID if first else (EPI_ADD_GRID | EPI_DACT)
-                g2 = dgrad_strided(g1, weight_storage(w1p), stride, x.shape[1:3], act=act, epilogue=epi, add_grid=dxb, dsrc=None if first else xd)
+                if ub1 is not None and tuple(stride) != (1, 1):       # (pixel-pair Winograd: forward took the layer)
+                    g2 = wino_strided_dgrad(g1, ub1, cin, stride, x.shape[1:3], act=act, epilogue=epi, add_grid=dxb, dsrc=None if first else xd)
+                else:
+                    g2 = dgrad_strided(g1, weight_storage(w1p), stride, x.shape[1:3], act=act, epilogue=epi, add_grid=dxb, dsrc=None if first else xd)
         pending.flush()
         if BACKWARD_TRACE is not None:
             BACKWARD_TRACE.append(("segment", blocks[0][0], blocks[-1][1], nb))

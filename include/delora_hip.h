@@ -474,6 +474,32 @@ int dl_wino_conv3x3_nhwc_f32(const float* x, const float* u, float* y, const flo
                              dl_stream stream);
 
 /*
+ * Stride-(1,2) 3x3 layers (wrap-around columns, zero rows) on the same fused Winograd kernel.  With an even width the layer is a
+ * stride-1 3x3 convolution of the same memory read as [N][H][W/2][2C] (a pixel pair = one pixel with 2C channels) whose kernel has no
+ * tap in its third column: a quarter of the Winograd planes is identically zero and is neither fetched nor multiplied (12 instead of
+ * the direct form's 18 multiply-adds per output and (c, k) pair).  H, W, C, K always describe the LAYER: x [N][H][W][C], y and g
+ * [N][H][W/2][K], w [K][3][3][C].
+ *   dl_wino_strided_takes:        1 when the dispatch should take the layer (stride (1,2); H even, W % 4 == 0; C, K multiples of 64; the
+ *                                 pair view divides into 2x32 or 4x16 tile groups; enough tile groups that the stride-1 dispatch would not
+ *                                 split the channels at `cu_count` CUs), else 0.  cu_count > 0 answers without a GPU; <= 0: this device.
+ *   dl_wino_strided_weights_f32:  w -> u_fwd and/or u_bwd, dl_wino_strided_weights_floats (= 16 K 2C) floats each, once per step.
+ *   dl_wino_strided_conv3x3_nhwc_f32:  forward; epilogue 0 or the activation bit (2).
+ *   dl_wino_strided_dgrad3x3_nhwc_f32: input gradient dx [N][H][W][C]; epilogue bits as dl_conv2d_dgrad_strided_nhwc_f32: 8 adds
+ *                                 add_grid, the compact [N][H][W/2][C] gradient of the 1x1 down-sampling branch, onto the even pixels;
+ *                                 4 multiplies by act'(dsrc), dsrc [N][H][W][C].
+ * The two convolutions run every shape that tiles, whatever dl_wino_strided_takes answers.  Other shapes: DL_ERR_UNSUPPORTED.
+ */
+int dl_wino_strided_takes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t K, int32_t stride_h, int32_t stride_w, int32_t cu_count);
+size_t dl_wino_strided_weights_floats(int32_t K, int32_t C, int32_t stride_h, int32_t stride_w);
+int dl_wino_strided_weights_f32(const float* w, float* u_fwd, float* u_bwd, int32_t K, int32_t C, int32_t stride_h, int32_t stride_w,
+                                dl_stream stream);
+int dl_wino_strided_conv3x3_nhwc_f32(const float* x, const float* u_fwd, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t K,
+                                     int32_t stride_h, int32_t stride_w, int32_t act, uint32_t epilogue, dl_stream stream);
+int dl_wino_strided_dgrad3x3_nhwc_f32(const float* g, const float* u_bwd, float* dx, const float* add_grid, const float* dsrc, int32_t N,
+                                      int32_t H, int32_t W, int32_t K, int32_t C, int32_t stride_h, int32_t stride_w, int32_t act,
+                                      uint32_t epilogue, dl_stream stream);
+
+/*
  * Weight gradient of a stride-1 3x3 layer in the Winograd domain (2.25x fewer multiplications than
  * dl_conv2d_wgrad_nhwc_f32; partial sums in a fixed order): x [N][H][W][C], g [N][H][W][K] -> dw [K][3][3][C].
  * Any image size (partial 2x2 tiles at odd edges, overhanging chunks of 8 tiles); C and K multiples of 64;

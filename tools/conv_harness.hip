@@ -3,6 +3,7 @@
 //   conv_harness time [reps]      the pose CNN's layer shapes at batch 8 (64x2048 input): us, TFLOP/s, fraction of 157.3
 //   conv_harness peak             sustained fp32 MFMA rate of the whole chip (no memory traffic) and the shader clock under it
 //   conv_harness tune [reps]      the stride-1 3x3 layers with every tile variant of the tuning build
+//   conv_harness strided [reps]   the stride-(1,2) 3x3 layers: direct kernel, pixel-pair Winograd (12 planes) and its 16-plane form
 // Build: make -C tools   (compiles ../delora_amd/csrc/conv.hip into the binary with -DCV_TUNE: no library needed)
 #include <hip/hip_runtime.h>
 
@@ -342,6 +343,41 @@ static void time_wino(const Shape& s, int reps, std::mt19937& gen) {
   CK(hipFree(dx)); CK(hipFree(dw)); CK(hipFree(dg)); CK(hipFree(dy)); CK(hipFree(dgi)); CK(hipFree(uf)); CK(hipFree(ub));
 }
 
+// A stride-(1,2) 3x3 layer three ways: the direct kernel, the pixel-pair Winograd kernel (12 of 16 planes), and the same pixel-pair
+// weights through the stride-1 entry point on the reinterpreted shape [N][H][W/2][2C] (all 16 planes; forward and plain input gradient --
+// that entry point cannot add the grid operand).  Forward with tanh, input gradient with tanh' as the step runs them.
+static void time_strided(const Shape& s, int reps, std::mt19937& gen) {
+  const int Wo = s.W / 2;
+  const size_t nx = (size_t)s.N * s.H * s.W * s.C, ny = (size_t)s.N * s.H * Wo * s.K, nw = (size_t)s.K * 9 * s.C;
+  auto x = rnd(nx, gen, 1.f), w = rnd(nw, gen, 0.05f), g = rnd(ny, gen, 1.f), ag = rnd(nx / 2, gen, 1.f);
+  float *dx = dev(x), *dw = dev(w), *dg = dev(g), *dag = dev(ag), *dy, *dgi, *uf, *ub;
+  const size_t nu = dl_wino_strided_weights_floats(s.K, s.C, 1, 2);
+  CK(hipMalloc(&dy, ny * sizeof(float))); CK(hipMalloc(&dgi, nx * sizeof(float)));
+  CK(hipMalloc(&uf, nu * sizeof(float))); CK(hipMalloc(&ub, nu * sizeof(float)));
+  hipEvent_t a, b;
+  CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
+  auto run = [&](const char* what, auto fn) {
+    if (fn()) { printf("%-26s %-18s unsupported: %s\n", s.name, what, dl_last_error()); return; }
+    CK(hipDeviceSynchronize());
+    CK(hipEventRecord(a));
+    for (int i = 0; i < reps; ++i) fn();
+    CK(hipEventRecord(b));
+    CK(hipEventSynchronize(b));
+    float ms;
+    CK(hipEventElapsedTime(&ms, a, b));
+    printf("%-26s %-18s %9.1f us\n", s.name, what, 1e3 * ms / reps);
+  };
+  printf("%-26s takes: %d\n", s.name, dl_wino_strided_takes(s.N, s.H, s.W, s.C, s.K, 1, 2, 0));
+  run("direct fwd", [&] { return dl_conv2d_nhwc_f32(dx, dw, dy, nullptr, nullptr, s.N, s.H, s.W, s.C, s.K, 3, 1, 2, 0, 1, DL_CONV_ACT, nullptr); });
+  run("direct dgrad", [&] { return dl_conv2d_dgrad_strided_nhwc_f32(dg, dw, dgi, dag, dx, s.N, s.H, s.W, s.K, s.C, 3, 1, 2, 0, 1, 8 | DL_CONV_DACT, nullptr, nullptr); });
+  run("pair weights", [&] { return dl_wino_strided_weights_f32(dw, uf, ub, s.K, s.C, 1, 2, nullptr); });
+  run("pair fwd", [&] { return dl_wino_strided_conv3x3_nhwc_f32(dx, uf, dy, s.N, s.H, s.W, s.C, s.K, 1, 2, 1, DL_CONV_ACT, nullptr); });
+  run("pair dgrad", [&] { return dl_wino_strided_dgrad3x3_nhwc_f32(dg, ub, dgi, dag, dx, s.N, s.H, s.W, s.K, s.C, 1, 2, 1, 8 | DL_CONV_DACT, nullptr); });
+  run("pair fwd 16 planes", [&] { return dl_wino_conv3x3_nhwc_f32(dx, uf, dy, nullptr, nullptr, s.N, s.H, Wo, 2 * s.C, s.K, 1, DL_CONV_ACT, nullptr, nullptr); });
+  run("pair dgrad 16 planes", [&] { return dl_wino_conv3x3_nhwc_f32(dg, ub, dgi, nullptr, dx, s.N, s.H, Wo, s.K, 2 * s.C, 1, DL_CONV_DACT, nullptr, nullptr); });
+  CK(hipFree(dx)); CK(hipFree(dw)); CK(hipFree(dg)); CK(hipFree(dag)); CK(hipFree(dy)); CK(hipFree(dgi)); CK(hipFree(uf)); CK(hipFree(ub));
+}
+
 static void time_shape(const Shape& s, int reps, std::mt19937& gen, double* total_us, bool with_wgrad = true) {
   const int Ho = s.H / s.sh, Wo = s.W / s.sw;
   const size_t nx = (size_t)s.N * s.H * s.W * s.C, ny = (size_t)s.N * Ho * Wo * s.K, nw = (size_t)s.K * s.ks * s.ks * s.C;
@@ -472,6 +508,12 @@ int main(int argc, char** argv) {
       }
     }
     return bad ? 1 : 0;
+  }
+  if (argc >= 2 && !strcmp(argv[1], "strided")) {
+    const int reps = argc >= 3 ? atoi(argv[2]) : 20;
+    const Shape layers[] = {{"layer2.0.conv1 s(1,2)", 8, 64, 512, 64, 128, 3, 1, 2}, {"layer3.0.conv1 s(1,2)", 8, 64, 256, 128, 256, 3, 1, 2}};
+    for (const auto& s : layers) time_strided(s, reps, gen);
+    return 0;
   }
   if (argc >= 2 && !strcmp(argv[1], "tune")) {
     const int reps = argc >= 3 ? atoi(argv[2]) : 10;
