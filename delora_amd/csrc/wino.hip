@@ -702,20 +702,29 @@ template <bool NEG> __device__ __forceinline__ f32x2 w3_g23(f32x2 h, f32x2 c10) 
 
 struct W3Pos { int n, ta, b8; };
 
-__device__ __forceinline__ void wino_wgrad_body3(const WWArgs& a, const int blk) {
-  static_assert((2 * W3_BUF + W3_RAW + W3_GRAW) * 4 <= 163840, "LDS budget");
-  __shared__ __attribute__((aligned(16))) float lds[2 * W3_BUF + W3_RAW + W3_GRAW];
+// LIVE: the xi-columns b of the 4x4 domain that are computed (bit b).  0xF is the stride-1 layer.  The pixel-pair view of a stride-(1,2)
+// layer (x read as [N][H][W/2][2C]) has no tap in its third column, and its even-pixel channels have a tap in the
+// middle column only: dW = G^T dU G with the last row of G = (0, 0, 1) needs b in {0,1,2} (0x7) for the odd-pixel channel blocks and
+// b in {1,2} (0x6) for the even-pixel ones.  A dead column has no half planes (8 MFMAs per wave and chunk), no accumulators, no transform
+// pieces on either operand side and no store; the side work and the two barriers are re-placed over the half planes that remain.
+// a.C is then the pair view's 2C; the block's planes go to ws[slab][a][live b][K][C] of the block's own kind (a.ws, see k_wino_swgrad_batch).
+static_assert((2 * W3_BUF + W3_RAW + W3_GRAW) * 4 <= 163840, "LDS budget");
+__shared__ __attribute__((aligned(16))) float w3_lds[2 * W3_BUF + W3_RAW + W3_GRAW];      // one array for every column set a kernel instantiates
+template <int LIVE, bool UPPER = LIVE == 0x7>
+__device__ __forceinline__ void wino_wgrad_body3_live(const WWArgs& a, const int blk) {
+  static_assert(LIVE == 0xF || LIVE == 0x7 || LIVE == 0x6, "column sets with a schedule");
+  float* const lds = w3_lds;
   float* raw = lds + 2 * W3_BUF;
   float* graw = raw + W3_RAW;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, half = lane >> 5;
   const int mb = wave & 1, nb = (wave >> 1) & 1, xh = wave >> 2;
-  const int CT = a.C / 64;
+  const int CT = LIVE == 0xF ? a.C / 64 : a.C / 128;                                 // the 64-channel blocks of the launch / of one pixel phase
   int t = blk;
   const int slab = t % a.nslabs; t /= a.nslabs;
   const int ct = t % CT;
   const int kt = t / CT;
-  const int k0 = kt * 64, c0 = ct * 64;
+  const int k0 = kt * 64, c0 = ct * 64 + (UPPER ? a.C / 2 : 0);                      // (the odd pixels' channels are the pair's upper half)
   const int th = a.H / 2, tw8 = (a.W / 2) / 8;
   const int total_chunks = a.N * th * tw8;
   const int ch_begin = slab * a.chunks_per_slab;
@@ -816,6 +825,14 @@ __device__ __forceinline__ void wino_wgrad_body3(const WWArgs& a, const int blk)
 #define W3_GV(E, B)         { if ((B) == 0) { V01[E][0] = w3_g01<false>(P[0][2 * (E)], c01); V23[E][0] = w3_g23<false>(P[0][2 * (E)], c10); }              \
                               else if ((B) == 3) { V01[E][3] = w3_g01<true>(P[0][2 * (E) + 1], c01); V23[E][3] = w3_g23<true>(P[0][2 * (E) + 1], c10); } \
                               else { V01[E][B] = w3_g01<false>(T[E][B], c01); V23[E][B] = w3_g23<false>(T[E][B], c10); } }
+#define W3_B(B, ...)        { if constexpr ((LIVE >> (B)) & 1) { __VA_ARGS__ } }                            // a piece of column B, if it is live
+  // the patch columns the live xi-columns read: 0x7 columns 0-4, 0x6 columns 1-4 of the thread's six
+#define W3_DLD7_0A() W3_RD2(P[0][0], 0, 20) W3_RD2(P[0][1], 1, 21) W3_RD2(P[0][2], 2, 22)
+#define W3_DLD7_1A() W3_RD2(P[1][0], 40, 60) W3_RD2(P[1][1], 41, 61) W3_RD2(P[1][2], 42, 62)
+#define W3_DLD6_0A() W3_RD2(P[0][1], 1, 21) W3_RD2(P[0][2], 2, 22)
+#define W3_DLD6_1A() W3_RD2(P[1][1], 41, 61) W3_RD2(P[1][2], 42, 62)
+#define W3_DLDL_0B() W3_RD2(P[0][3], 3, 23) W3_RD2(P[0][4], 4, 24)
+#define W3_DLDL_1B() W3_RD2(P[1][3], 43, 63) W3_RD2(P[1][4], 44, 64)
 
 #define W3_FR_FROM(HP, BP)                                                                                                \
   {                                                                                                                       \
@@ -851,17 +868,20 @@ __device__ __forceinline__ void wino_wgrad_body3(const WWArgs& a, const int blk)
       W3_DLD_0A() W3_DLD_0B() W3_DLD_1A() W3_DLD_1B()
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       W3_DMASK()
-      W3_DT(0, 0, 0) W3_DT(0, 0, 1) W3_DT(0, 0, 2) W3_DT(0, 0, 3) W3_DT(0, 1, 0) W3_DT(0, 1, 1) W3_DT(0, 1, 2) W3_DT(0, 1, 3)
-      W3_DV(0, 0) W3_DV(0, 1) W3_DV(0, 2) W3_DV(0, 3)
-      W3_DT(1, 0, 0) W3_DT(1, 0, 1) W3_DT(1, 0, 2) W3_DT(1, 0, 3) W3_DT(1, 1, 0) W3_DT(1, 1, 1) W3_DT(1, 1, 2) W3_DT(1, 1, 3)
-      W3_DV(1, 0) W3_DV(1, 1) W3_DV(1, 2) W3_DV(1, 3)
-      W3_WR(W3_OPER, 0) W3_WR(W3_OPER, 1) W3_WR(W3_OPER, 2) W3_WR(W3_OPER, 3)
+      W3_B(0, W3_DT(0, 0, 0)) W3_B(1, W3_DT(0, 0, 1)) W3_B(2, W3_DT(0, 0, 2)) W3_B(3, W3_DT(0, 0, 3))
+      W3_B(0, W3_DT(0, 1, 0)) W3_B(1, W3_DT(0, 1, 1)) W3_B(2, W3_DT(0, 1, 2)) W3_B(3, W3_DT(0, 1, 3))
+      W3_B(0, W3_DV(0, 0)) W3_B(1, W3_DV(0, 1)) W3_B(2, W3_DV(0, 2)) W3_B(3, W3_DV(0, 3))
+      W3_B(0, W3_DT(1, 0, 0)) W3_B(1, W3_DT(1, 0, 1)) W3_B(2, W3_DT(1, 0, 2)) W3_B(3, W3_DT(1, 0, 3))
+      W3_B(0, W3_DT(1, 1, 0)) W3_B(1, W3_DT(1, 1, 1)) W3_B(2, W3_DT(1, 1, 2)) W3_B(3, W3_DT(1, 1, 3))
+      W3_B(0, W3_DV(1, 0)) W3_B(1, W3_DV(1, 1)) W3_B(2, W3_DV(1, 2)) W3_B(3, W3_DV(1, 3))
+      W3_B(0, W3_WR(W3_OPER, 0)) W3_B(1, W3_WR(W3_OPER, 1)) W3_B(2, W3_WR(W3_OPER, 2)) W3_B(3, W3_WR(W3_OPER, 3))
     } else {
       W3_GLD()
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       W3_GH(0) W3_GH(1)
-      W3_GV(0, 0) W3_GV(0, 1) W3_GV(0, 2) W3_GV(0, 3) W3_GV(1, 0) W3_GV(1, 1) W3_GV(1, 2) W3_GV(1, 3)
-      W3_WR(0, 0) W3_WR(0, 1) W3_WR(0, 2) W3_WR(0, 3)
+      W3_B(0, W3_GV(0, 0)) W3_B(1, W3_GV(0, 1)) W3_B(2, W3_GV(0, 2)) W3_B(3, W3_GV(0, 3))
+      W3_B(0, W3_GV(1, 0)) W3_B(1, W3_GV(1, 1)) W3_B(2, W3_GV(1, 2)) W3_B(3, W3_GV(1, 3))
+      W3_B(0, W3_WR(0, 0)) W3_B(1, W3_WR(0, 1)) W3_B(2, W3_WR(0, 2)) W3_B(3, W3_WR(0, 3))
     }
   }
   __syncthreads();
@@ -870,10 +890,11 @@ __device__ __forceinline__ void wino_wgrad_body3(const WWArgs& a, const int blk)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
+  constexpr int HP0 = LIVE & 1 ? 0 : 2;                   // the first live half plane
   f32x4 av[2], bv[2];
   {
     const float* cur = lds;
-    W3_FR(0)
+    W3_FR(HP0)
   }
   // Per iteration: half planes 0-1 multiply while every thread reads the patches of chunk ch + 1 (landed during the previous iteration);
   // barrier M (patches read); the DMA of chunk ch + 2 goes out and the transforms run, two packed instructions per MFMA, results to the
@@ -888,7 +909,86 @@ __device__ __forceinline__ void wino_wgrad_body3(const WWArgs& a, const int blk)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                    \
     __builtin_amdgcn_s_barrier();                                                                                         \
     __builtin_amdgcn_sched_barrier(0);
-  if (xh == 0) {
+#define W3_BAR_E()                                                                                                        \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                           \
+    __builtin_amdgcn_s_barrier();                                                                                         \
+    __builtin_amdgcn_sched_barrier(0);
+  // Fewer half planes: the iteration is rotated so that the DMA keeps the longest window the shorter chunk has.  The patch reads of chunk
+  // ch + 1 go behind the first MFMAs of the LAST half plane (after barrier E, its other MFMAs cover their latency), barrier M opens the
+  // next iteration, the DMA of chunk ch + 2 goes out behind its first MFMA and the transforms follow, at most two packed pieces per MFMA.
+  if constexpr (LIVE != 0xF) {                            // the reads of the first iteration
+    if (xh == 0) { if constexpr (LIVE == 0x7) { W3_DLD7_0A() W3_DLD7_1A() } else { W3_DLD6_0A() W3_DLD6_1A() } W3_DLDL_0B() W3_DLDL_1B() }
+    else { W3_GLD() }
+  }
+  if constexpr (LIVE == 0x7) {
+    // 6 half planes (24 MFMAs): barrier M, 0-4 || DMA + transforms of columns 0-2, barrier E, 5 || patch reads
+    if (xh == 0) {
+      for (int ch = ch_begin; ch < ch_end; ++ch) {
+        const float* cur = lds + ((ch - ch_begin) & 1) * W3_BUF;
+        float* nxt = lds + ((ch - ch_begin + 1) & 1) * W3_BUF;
+        const bool top = p1.ta == 0, bot = p1.ta == th - 1;
+        W3Pos p2 = p1;
+        if (ch + 2 < ch_end) advance(p2);
+        W3_BAR_M()
+        W3_M(0, 0, W3_FR(1) dma(p2);) W3_M(0, 1, W3_DMASK() W3_DT(0, 0, 0) W3_DT(0, 0, 1)) W3_M(0, 2, W3_DT(0, 0, 2) W3_DT(0, 1, 0)) W3_M(0, 3, W3_DT(0, 1, 1) W3_DT(0, 1, 2))
+        W3_M(1, 0, W3_FR(2) W3_DV(0, 0)) W3_M(1, 1, W3_DV(0, 1)) W3_M(1, 2, W3_DV(0, 2)) W3_M(1, 3, W3_DT(1, 0, 0) W3_DT(1, 0, 1))
+        W3_M(2, 0, W3_FR(3) W3_DT(1, 0, 2)) W3_M(2, 1, W3_DT(1, 1, 0) W3_DT(1, 1, 1)) W3_M(2, 2, W3_DT(1, 1, 2)) W3_M(2, 3, W3_DV(1, 0))
+        W3_M(3, 0, W3_FR(4) W3_WR(W3_OPER, 0)) W3_M(3, 1, W3_DV(1, 1)) W3_M(3, 2, W3_WR(W3_OPER, 1)) W3_M(3, 3, W3_DV(1, 2))
+        W3_M(4, 0, W3_FR(5) W3_WR(W3_OPER, 2)) W3_M(4, 1, ) W3_M(4, 2, ) W3_M(4, 3, )
+        W3_BAR_E()
+        W3_M(5, 0, W3_FR_FROM(0, nxt) W3_DLD7_0A() W3_DLDL_0B()) W3_M(5, 1, W3_DLD7_1A() W3_DLDL_1B()) W3_M(5, 2, ) W3_M(5, 3, )
+        p1 = p2;
+      }
+    } else {
+      for (int ch = ch_begin; ch < ch_end; ++ch) {
+        const float* cur = lds + ((ch - ch_begin) & 1) * W3_BUF;
+        float* nxt = lds + ((ch - ch_begin + 1) & 1) * W3_BUF;
+        W3Pos p2 = p1;
+        if (ch + 2 < ch_end) advance(p2);
+        W3_BAR_M()
+        W3_M(0, 0, W3_FR(1) dma(p2);) W3_M(0, 1, W3_GH(0)) W3_M(0, 2, W3_GV(0, 0)) W3_M(0, 3, W3_GV(0, 1))
+        W3_M(1, 0, W3_FR(2)) W3_M(1, 1, W3_GV(0, 2)) W3_M(1, 2, W3_GH(1)) W3_M(1, 3, W3_GV(1, 0))
+        W3_M(2, 0, W3_FR(3) W3_WR(0, 0)) W3_M(2, 1, W3_GV(1, 1)) W3_M(2, 2, W3_WR(0, 1)) W3_M(2, 3, W3_GV(1, 2))
+        W3_M(3, 0, W3_FR(4) W3_WR(0, 2)) W3_M(3, 1, ) W3_M(3, 2, ) W3_M(3, 3, )
+        W3_M(4, 0, W3_FR(5)) W3_M(4, 1, ) W3_M(4, 2, ) W3_M(4, 3, )
+        W3_BAR_E()
+        W3_M(5, 0, W3_FR_FROM(0, nxt) W3_GLD()) W3_M(5, 1, ) W3_M(5, 2, ) W3_M(5, 3, )
+        p1 = p2;
+      }
+    }
+  } else if constexpr (LIVE == 0x6) {
+    // 4 half planes (16 MFMAs): barrier M, 2-4 || DMA + transforms of columns 1-2, barrier E, 5 || patch reads
+    if (xh == 0) {
+      for (int ch = ch_begin; ch < ch_end; ++ch) {
+        const float* cur = lds + ((ch - ch_begin) & 1) * W3_BUF;
+        float* nxt = lds + ((ch - ch_begin + 1) & 1) * W3_BUF;
+        const bool top = p1.ta == 0, bot = p1.ta == th - 1;
+        W3Pos p2 = p1;
+        if (ch + 2 < ch_end) advance(p2);
+        W3_BAR_M()
+        W3_M(2, 0, W3_FR(3) dma(p2);) W3_M(2, 1, W3_DMASK() W3_DT(0, 0, 1) W3_DT(0, 0, 2)) W3_M(2, 2, W3_DT(0, 1, 1) W3_DT(0, 1, 2)) W3_M(2, 3, W3_DV(0, 1))
+        W3_M(3, 0, W3_FR(4) W3_DV(0, 2)) W3_M(3, 1, W3_DT(1, 0, 1) W3_DT(1, 0, 2)) W3_M(3, 2, W3_DT(1, 1, 1) W3_DT(1, 1, 2)) W3_M(3, 3, W3_DV(1, 1))
+        W3_M(4, 0, W3_FR(5) W3_WR(W3_OPER, 1)) W3_M(4, 1, W3_DV(1, 2)) W3_M(4, 2, W3_WR(W3_OPER, 2)) W3_M(4, 3, )
+        W3_BAR_E()
+        W3_M(5, 0, W3_FR_FROM(2, nxt) W3_DLD6_0A() W3_DLDL_0B()) W3_M(5, 1, W3_DLD6_1A() W3_DLDL_1B()) W3_M(5, 2, ) W3_M(5, 3, )
+        p1 = p2;
+      }
+    } else {
+      for (int ch = ch_begin; ch < ch_end; ++ch) {
+        const float* cur = lds + ((ch - ch_begin) & 1) * W3_BUF;
+        float* nxt = lds + ((ch - ch_begin + 1) & 1) * W3_BUF;
+        W3Pos p2 = p1;
+        if (ch + 2 < ch_end) advance(p2);
+        W3_BAR_M()
+        W3_M(2, 0, W3_FR(3) dma(p2);) W3_M(2, 1, W3_GH(0)) W3_M(2, 2, W3_GV(0, 1)) W3_M(2, 3, W3_GV(0, 2))
+        W3_M(3, 0, W3_FR(4)) W3_M(3, 1, W3_GH(1)) W3_M(3, 2, W3_GV(1, 1)) W3_M(3, 3, W3_GV(1, 2))
+        W3_M(4, 0, W3_FR(5) W3_WR(0, 1)) W3_M(4, 1, W3_WR(0, 2)) W3_M(4, 2, ) W3_M(4, 3, )
+        W3_BAR_E()
+        W3_M(5, 0, W3_FR_FROM(2, nxt) W3_GLD()) W3_M(5, 1, ) W3_M(5, 2, ) W3_M(5, 3, )
+        p1 = p2;
+      }
+    }
+  } else if (xh == 0) {
     for (int ch = ch_begin; ch < ch_end; ++ch) {
       const float* cur = lds + ((ch - ch_begin) & 1) * W3_BUF;
       float* nxt = lds + ((ch - ch_begin + 1) & 1) * W3_BUF;
@@ -952,19 +1052,50 @@ __device__ __forceinline__ void wino_wgrad_body3(const WWArgs& a, const int blk)
 #undef W3_FR
 #undef W3_FR_FROM
 #undef W3_M
+#undef W3_B
+#undef W3_BAR_E
+#undef W3_DLD7_0A
+#undef W3_DLD7_1A
+#undef W3_DLD6_0A
+#undef W3_DLD6_1A
+#undef W3_DLDL_0B
+#undef W3_DLDL_1B
   // partial of this slab: ws[slab][xi][k0 + m][c0 + n]; accumulator register q of lane (li, half) is
   // row m = mb*32 + 8*(q/4) + 4*half + q%4, column n = nb*32 + li; accumulator xl = (a & 1) * 4 + b is plane xi = xh * 8 + xl
-  float* wp = a.ws + ((size_t)slab * 16) * a.K * a.C;
+  if constexpr (LIVE == 0xF) {
+    float* wp = a.ws + ((size_t)slab * 16) * a.K * a.C;
 #pragma unroll
-  for (int xl = 0; xl < 8; ++xl) {
-    const int xi = xh * 8 + xl;
+    for (int xl = 0; xl < 8; ++xl) {
+      const int xi = xh * 8 + xl;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int m = mb * 32 + 8 * (q / 4) + 4 * half + (q % 4);
-      wp[((size_t)xi * a.K + k0 + m) * a.C + c0 + nb * 32 + li] = acc[xl][q];
+      for (int q = 0; q < 16; ++q) {
+        const int m = mb * 32 + 8 * (q / 4) + 4 * half + (q % 4);
+        wp[((size_t)xi * a.K + k0 + m) * a.C + c0 + nb * 32 + li] = acc[xl][q];
+      }
+    }
+  } else {
+    // live planes only, of the block's own pixel phase: ws[slab][a][live b][K][C]  (C = a.C / 2 channels of the layer)
+    constexpr int NB = (LIVE & 1) + ((LIVE >> 1) & 1) + ((LIVE >> 2) & 1) + ((LIVE >> 3) & 1);
+    const int CL = a.C / 2, cl0 = c0 >= CL ? c0 - CL : c0;
+    float* wp = a.ws + ((size_t)slab * 4 * NB) * a.K * CL;
+#pragma unroll
+    for (int xl = 0; xl < 8; ++xl) {
+      const int b = xl & 3;
+      if (!((LIVE >> b) & 1)) continue;
+      int bi = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bi += (j < b && ((LIVE >> j) & 1)) ? 1 : 0;
+      const int plane = (xh * 2 + (xl >> 2)) * NB + bi;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int m = mb * 32 + 8 * (q / 4) + 4 * half + (q % 4);
+        wp[((size_t)plane * a.K + k0 + m) * CL + cl0 + nb * 32 + li] = acc[xl][q];
+      }
     }
   }
 }
+
+__device__ __forceinline__ void wino_wgrad_body3(const WWArgs& a, const int blk) { wino_wgrad_body3_live<0xF>(a, blk); }
 
 template <bool RAG>
 __global__ __launch_bounds__(WW_THREADS) void k_wino_wgrad(WWArgs a) {
@@ -994,6 +1125,30 @@ __global__ __launch_bounds__(WW_THREADS) void k_wino_wgrad_batch(WWBatchArgs b) 
   else
 #endif
   wino_wgrad_body<RAG>(a, (int)blockIdx.x - b.first_wg[l]);
+}
+
+// Weight gradients of stride-(1,2) 3x3 layers on the pixel-pair view (dl_wino_strided_wgrad3x3_batch_nhwc_f32).  A layer is TWO items of
+// the table: its odd-pixel channel blocks (pair channels >= C: 12 live planes) and its even-pixel ones (8 live planes).  The two kinds
+// cost different time per chunk, so each has its own slab plan and its own partials; which body runs is workgroup-uniform.  One launch
+// with both bodies: each stays below the stride-1 body's registers, and a second launch would leave the chip idle at the tail of the first.
+#define SW_ITEMS (2 * DL_WGRAD_BATCH)
+struct SWBatchArgs {
+  WWArgs item[SW_ITEMS];                 // the pair view: W = W/2 pixels of C = 2C channels; ws = the item's own partials
+  int first_wg[SW_ITEMS + 1];
+  int odd[SW_ITEMS];
+  int n;
+};
+// ALL12 (DL_SWGRAD_ALL12=1, a measurement switch of tools/conv_harness): the even-pixel blocks run the 12-plane body as well
+template <bool ALL12>
+__global__ __launch_bounds__(WW_THREADS) void k_wino_wgrad_strided_batch(SWBatchArgs b) {
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < SW_ITEMS; ++i)
+    if (i < b.n && (int)blockIdx.x >= b.first_wg[i]) l = i;
+  const WWArgs a = b.item[l];
+  if (b.odd[l]) wino_wgrad_body3_live<0x7>(a, (int)blockIdx.x - b.first_wg[l]);
+  else if constexpr (ALL12) wino_wgrad_body3_live<0x7, false>(a, (int)blockIdx.x - b.first_wg[l]);
+  else wino_wgrad_body3_live<0x6>(a, (int)blockIdx.x - b.first_wg[l]);
 }
 
 // U[xi][k][c] = sum over slabs of ws[slab][xi][k][c] in a fixed order (deterministic), four channels per thread
@@ -1226,6 +1381,204 @@ extern "C" int dl_wino_wgrad3x3_batch_nhwc_f32(const dl_wgrad_layer* layers, int
   if (sum.n) DL_LAUNCH_PLAIN(k_wino_wgrad_sum_batch, dim3(sum_blocks), dim3(256), st, sum);
   DL_LAUNCH_PLAIN(k_wino_wgrad_out_batch, dim3(out_blocks), dim3(256), st, out);
   return dl_check_launch("dl_wino_wgrad3x3_batch_nhwc_f32");
+}
+
+// ---- stride-(1,2) layers: the pixel-pair view's live planes (k_wino_wgrad_strided_batch)
+struct SWSumArgs {
+  const float* src[SW_ITEMS];
+  float* dst[SW_ITEMS];
+  int count4[SW_ITEMS], nslabs[SW_ITEMS];
+  int first_block[SW_ITEMS + 1];
+  int n;
+};
+__global__ __launch_bounds__(256) void k_wino_wgrad_strided_sum_batch(SWSumArgs b) {
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < SW_ITEMS; ++i)
+    if (i < b.n && (int)blockIdx.x >= b.first_block[i]) l = i;
+  wino_wgrad_sum_body(b.src[l], b.nslabs[l], (size_t)b.count4[l], b.dst[l], (size_t)((int)blockIdx.x - b.first_block[l]) * 256 + threadIdx.x);
+}
+// dw [K][3][3][C] of the layer from the summed live planes: uo [4][3][K][C] (odd pixels: b = 0, 1, 2), ue [4][2][K][C] (even pixels: b = 1, 2).
+// The pair kernel's tap columns (dW G of the live columns; its third column does not exist):
+//   dw[k][r][0][c] = column 0 of pair channel C + c,  dw[k][r][1][c] = column 1 of pair channel c,  dw[k][r][2][c] = column 1 of pair channel C + c
+struct SWOutArgs {
+  const float* uo[DL_WGRAD_BATCH];
+  const float* ue[DL_WGRAD_BATCH];
+  float* dw[DL_WGRAD_BATCH];
+  int K[DL_WGRAD_BATCH], C[DL_WGRAD_BATCH];
+  int first_block[DL_WGRAD_BATCH + 1];
+  int n, eb;                            // eb: live columns the even-pixel planes hold (2; 3 under DL_SWGRAD_ALL12, the first unused)
+};
+__device__ __forceinline__ float sw_gt(int rr, float u0, float u1, float u2, float u3) {     // row rr of G^T = [[1, 1/2, 1/2, 0], [0, 1/2, -1/2, 0], [0, 1/2, 1/2, 1]]
+  return rr == 0 ? u0 + 0.5f * (u1 + u2) : rr == 1 ? 0.5f * (u1 - u2) : 0.5f * (u1 + u2) + u3;
+}
+__global__ __launch_bounds__(256) void k_wino_wgrad_strided_out_batch(SWOutArgs b) {
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < DL_WGRAD_BATCH; ++i)
+    if (i < b.n && (int)blockIdx.x >= b.first_block[i]) l = i;
+  const int K = b.K[l], C = b.C[l];
+  const size_t i = (size_t)((int)blockIdx.x - b.first_block[l]) * 256 + threadIdx.x;
+  if (i >= (size_t)K * C) return;
+  const int k = (int)(i / C), c = (int)(i % C);
+  const float* __restrict__ uo = b.uo[l];
+  const float* __restrict__ ue = b.ue[l];
+  float* __restrict__ dw = b.dw[l];
+  float o[4][3], e[4][2];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o[a][j] = uo[((size_t)(a * 3 + j) * K + k) * C + c];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) e[a][j] = ue[((size_t)(a * b.eb + b.eb - 2 + j) * K + k) * C + c];
+  }
+#pragma unroll
+  for (int rr = 0; rr < 3; ++rr) {
+    const float p0 = sw_gt(rr, o[0][0], o[1][0], o[2][0], o[3][0]);
+    const float p1 = sw_gt(rr, o[0][1], o[1][1], o[2][1], o[3][1]);
+    const float p2 = sw_gt(rr, o[0][2], o[1][2], o[2][2], o[3][2]);
+    const float q1 = sw_gt(rr, e[0][0], e[1][0], e[2][0], e[3][0]);
+    const float q2 = sw_gt(rr, e[0][1], e[1][1], e[2][1], e[3][1]);
+    dw[(((size_t)k * 3 + rr) * 3 + 0) * C + c] = p0 + 0.5f * (p1 + p2);
+    dw[(((size_t)k * 3 + rr) * 3 + 1) * C + c] = 0.5f * (q1 - q2);
+    dw[(((size_t)k * 3 + rr) * 3 + 2) * C + c] = 0.5f * (p1 - p2);
+  }
+}
+
+static bool sw_takes(int N, int H, int W, int C, int K, int sh, int sw) {
+  return sh == 1 && sw == 2 && N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && !(H & 1) && W % 32 == 0 && C % 64 == 0 && K % 64 == 0 &&
+         ww_supported(N, H, W / 2, 2 * C, K);
+}
+/* see include/delora_hip.h */
+extern "C" int dl_wino_strided_wgrad_takes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t K, int32_t stride_h, int32_t stride_w) {
+  return sw_takes(N, H, W, C, K, stride_h, stride_w) ? 1 : 0;
+}
+
+namespace {
+// An even-pixel block runs 16 of the odd-pixel block's 24 MFMAs per chunk, with the same DMA, barriers and per-column side work: the plan
+// weighs its chunks 3/4 (between the 2/3 of the matrix work alone and the 0.84-0.89 that dropping a quarter of k_wino_conv's planes left
+// of its time, profiles/strided_wino_harness.txt).
+struct SWItem {
+  WWArgs a;              // pair view; ws / nslabs / chunks_per_slab of this item
+  float* usum;
+  int odd, layer, tiles, planes;
+};
+bool sw_all12() {
+  static const bool on = [] { const char* e = getenv("DL_SWGRAD_ALL12"); return e && e[0] == '1'; }();
+  return on;
+}
+int sw_batch_plan(const dl_wgrad_layer* L, int n, std::vector<SWItem>& items) {
+  const char* me = "dl_wino_strided_wgrad3x3_batch_nhwc_f32";
+  if (!L || n <= 0 || n > DL_WGRAD_BATCH) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: 1..%d layers per call", me, DL_WGRAD_BATCH);
+  for (int i = 0; i < n; ++i) {
+    const dl_wgrad_layer& l = L[i];
+    if (l.ksize != 3) return dl_fail(DL_ERR_UNSUPPORTED, "%s: layer %d: ksize %d (must be 3)", me, i, l.ksize);
+    if (l.stride_h != 1 || l.stride_w != 2) return dl_fail(DL_ERR_UNSUPPORTED, "%s: layer %d: stride_h, stride_w (%d,%d) (must be (1,2))", me, i, l.stride_h, l.stride_w);
+    if (l.H <= 0 || (l.H & 1)) return dl_fail(DL_ERR_UNSUPPORTED, "%s: layer %d: H %d (must be even)", me, i, l.H);
+    if (l.W <= 0 || l.W % 32) return dl_fail(DL_ERR_UNSUPPORTED, "%s: layer %d: W %d (must be a multiple of 32)", me, i, l.W);
+    if (l.C <= 0 || l.C % 64) return dl_fail(DL_ERR_UNSUPPORTED, "%s: layer %d: C %d (must be a multiple of 64)", me, i, l.C);
+    if (l.K <= 0 || l.K % 64) return dl_fail(DL_ERR_UNSUPPORTED, "%s: layer %d: K %d (must be a multiple of 64)", me, i, l.K);
+    if (!sw_takes(l.N, l.H, l.W, l.C, l.K, 1, 2))
+      return dl_fail(DL_ERR_UNSUPPORTED, "%s: layer %d: N %d with H=%d W=%d C=%d K=%d (positive, below 2^31 elements and 2^30 per sample)", me, i, l.N, l.H, l.W, l.C, l.K);
+  }
+  items.resize(2 * n);
+  std::vector<int> tl(2 * n), ch(2 * n), ns(2 * n);
+  for (int i = 0; i < n; ++i) {
+    const dl_wgrad_layer& l = L[i];
+    const int chunks = l.N * (l.H / 2) * (l.W / 32);
+    for (int odd = 1; odd >= 0; --odd) {
+      SWItem& it = items[2 * i + (1 - odd)];
+      it.a = WWArgs{(const float*)l.x, (const float*)l.g, nullptr, l.N, l.H, l.W / 2, 2 * l.C, l.K, 0, 0};
+      it.usum = nullptr; it.odd = odd; it.layer = i;
+      it.tiles = (l.K / 64) * (l.C / 64);
+      it.planes = odd || sw_all12() ? 12 : 8;
+      tl[2 * i + (1 - odd)] = it.tiles;
+      ch[2 * i + (1 - odd)] = it.planes == 12 ? chunks : (3 * chunks + 3) / 4;
+    }
+  }
+  dl_plan_batch(tl.data(), ch.data(), 2 * n, 256, 10, ns.data());                      // one 512-thread workgroup per CU
+  for (int j = 0; j < 2 * n; ++j) {
+    SWItem& it = items[j];
+    const int chunks = it.a.N * (it.a.H / 2) * (it.a.W / 16);
+    const int want = ns[j] < chunks ? ns[j] : chunks;
+    it.a.chunks_per_slab = (chunks + want - 1) / want;
+    it.a.nslabs = (chunks + it.a.chunks_per_slab - 1) / it.a.chunks_per_slab;
+  }
+  return DL_OK;
+}
+}  // namespace
+
+/* see include/delora_hip.h */
+extern "C" size_t dl_wino_strided_wgrad3x3_batch_workspace_bytes(const dl_wgrad_layer* layers, int32_t n) {
+  std::vector<SWItem> items;
+  if (sw_batch_plan(layers, n, items)) return 0;
+  size_t floats = 0;
+  for (const auto& it : items) floats += ((size_t)(it.a.nslabs > 1 ? it.a.nslabs : 0) + 1) * it.planes * it.a.K * (it.a.C / 2);
+  return floats * sizeof(float);
+}
+
+extern "C" int dl_wino_strided_wgrad3x3_batch_nhwc_f32(const dl_wgrad_layer* layers, int32_t n, void* workspace, dl_stream stream) {
+  if (!workspace) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_wino_strided_wgrad3x3_batch_nhwc_f32: null workspace");
+  std::vector<SWItem> items;
+  const int rc0 = sw_batch_plan(layers, n, items);
+  if (rc0) return rc0;
+  for (int i = 0; i < n; ++i)
+    if (!layers[i].x || !layers[i].g || !layers[i].dw) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_wino_strided_wgrad3x3_batch_nhwc_f32: layer %d: null pointer", i);
+  hipStream_t st = (hipStream_t)stream;
+  float* wsf = (float*)workspace;
+  for (auto& it : items) {                               // [slab partials (only when split)] [their sum]
+    const size_t plane = (size_t)it.planes * it.a.K * (it.a.C / 2);
+    if (it.a.nslabs > 1) { it.a.ws = wsf; wsf += (size_t)it.a.nslabs * plane; it.usum = wsf; wsf += plane; }
+    else { it.a.ws = wsf; it.usum = wsf; wsf += plane; }  // a single slab IS the sum
+  }
+  std::vector<const SWItem*> grp;
+  for (const auto& it : items) grp.push_back(&it);
+  std::stable_sort(grp.begin(), grp.end(), [](const SWItem* x, const SWItem* y) {        // by decreasing time per workgroup (chunks x MFMAs per chunk)
+    return x->a.chunks_per_slab * (x->planes / 4 + 1) > y->a.chunks_per_slab * (y->planes / 4 + 1);
+  });
+  SWBatchArgs b{};
+  b.n = (int)grp.size();
+  int wgs = 0;
+  double flop = 0, bytes = 0;
+  for (int i = 0; i < b.n; ++i) {
+    const WWArgs& a = grp[i]->a;
+    b.item[i] = a;
+    b.odd[i] = grp[i]->odd;
+    b.first_wg[i] = wgs;
+    wgs += grp[i]->tiles * a.nslabs;
+    // the live planes' multiply-adds: 2 . {12 | 8} . tiles . 64 . 64 per block
+    flop += 2.0 * grp[i]->planes * (double)a.N * (a.H / 2) * (a.W / 2) * 64.0 * 64.0 * grp[i]->tiles;
+    if (grp[i]->odd) bytes += 4.0 * ((double)a.N * a.H * a.W * (a.C + a.K) + 9.0 * (a.C / 2) * a.K);
+  }
+  b.first_wg[b.n] = wgs;
+  const dl_wgrad_layer& f = layers[grp[0]->layer];
+  const DlProfTag tag{"k_wino_wgrad_strided", n > 1 ? "wgrad-batch" : "wgrad", f.N, f.H, f.W, f.C, f.K, 3, 1, 2, flop, bytes};
+  if (sw_all12()) DL_LAUNCH(tag, k_wino_wgrad_strided_batch<true>, dim3(wgs), dim3(WW_THREADS), st, b);
+  else DL_LAUNCH(tag, k_wino_wgrad_strided_batch<false>, dim3(wgs), dim3(WW_THREADS), st, b);
+  for (int i = 0; i < b.n; ++i) DL_PLAN_NOTE("%s slabs=%d", b.odd[i] ? "odd" : "even", b.item[i].nslabs);
+  SWSumArgs sum{};
+  SWOutArgs out{};
+  int sum_blocks = 0, out_blocks = 0;
+  for (const auto& it : items) {
+    if (it.a.nslabs > 1) {
+      const size_t count4 = (size_t)it.planes * it.a.K * (it.a.C / 2) / 4;
+      sum.src[sum.n] = it.a.ws; sum.dst[sum.n] = it.usum; sum.count4[sum.n] = (int)count4; sum.nslabs[sum.n] = it.a.nslabs;
+      sum.first_block[sum.n] = sum_blocks;
+      sum_blocks += (int)((count4 + 255) / 256);
+      ++sum.n;
+    }
+    if (it.odd) out.uo[it.layer] = it.usum; else out.ue[it.layer] = it.usum;
+  }
+  for (int i = 0; i < n; ++i) {
+    out.dw[i] = layers[i].dw; out.K[i] = layers[i].K; out.C[i] = layers[i].C;
+    out.first_block[i] = out_blocks;
+    out_blocks += (int)(((size_t)layers[i].K * layers[i].C + 255) / 256);
+  }
+  out.n = n; out.eb = sw_all12() ? 3 : 2;
+  sum.first_block[sum.n] = sum_blocks; out.first_block[n] = out_blocks;
+  if (sum.n) DL_LAUNCH_PLAIN(k_wino_wgrad_strided_sum_batch, dim3(sum_blocks), dim3(256), st, sum);
+  DL_LAUNCH_PLAIN(k_wino_wgrad_strided_out_batch, dim3(out_blocks), dim3(256), st, out);
+  return dl_check_launch("dl_wino_strided_wgrad3x3_batch_nhwc_f32");
 }
 
 // Sum of the channel ranges of a split launch + the layer's epilogue (as in k_wino_conv: shortcut add, activation, activation

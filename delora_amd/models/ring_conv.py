@@ -150,12 +150,28 @@ def _wgrad_batch_call(items, size_fn, run_fn, what, *extra):
     return out
 
 
+USE_WINOGRAD_STRIDED_WGRAD = True    # stride-(1,2) 3x3 weight gradients on the pixel-pair view, live planes only (honoured only with USE_WINOGRAD)
+# Dispatch policy on top of the shape rule: chunks of 8 tiles the pair view has per output block.  Below one chunk per CU a block's slabs
+# cannot fill the chip and every workgroup is prologue and plane stores only; nothing that small was measured, so it stays direct.
+WINO_STRIDED_WGRAD_MIN_CHUNKS = 256
+
+
+def wino_strided_wgrad_ok(N, H, W, C, K, stride):
+    """The shape rule of ``dl_wino_strided_wgrad_takes``, restated (no library call per layer and step): stride (1,2), even H, W a multiple
+    of 32, C and K multiples of 64, the pair view ``[N,H,W/2,2C]`` / ``[N,H,W/2,K]`` within the 32-bit offsets of the kernel."""
+    if tuple(stride) != (1, 2) or min(N, H, W, C, K) <= 0 or H % 2 or W % 32 or C % 64 or K % 64:
+        return False
+    wide = max(2 * C, K)
+    return N * H * (W // 2) * wide < 2 ** 31 and H * (W // 2) * wide < 2 ** 30
+
+
 def wgrad_batch(items):
     """The fp32 weight gradients of several layers in merged launches (include/delora_hip.h: ``dl_wgrad_layer``): ``items`` = list of
     (x, g, ks, stride); returns ``dW [K,k,k,C]`` per item.  Stride-1 3x3 layers with at least 128 input channels take the Winograd-domain
-    kernel (as ``wgrad_nhwc`` decides), the rest the direct one; within each family the layers that share a kernel run in ONE launch
+    kernel (as ``wgrad_nhwc`` decides), stride-(1,2) 3x3 layers that ``wino_strided_wgrad_ok`` takes and that are large enough the
+    pixel-pair form of it (``USE_WINOGRAD_STRIDED_WGRAD``), the rest the direct one; within each family the layers that share a kernel run in ONE launch
     with far fewer pixel slabs (fp32 partial copies of the gradient) per layer than a launch of their own needs."""
-    wino, direct = [], []
+    wino, strided, direct = [], [], []
     for i, (x, g, ks, stride) in enumerate(items):
         N, H, W, C = x.shape
         K = g.shape[3]
@@ -163,9 +179,16 @@ def wgrad_batch(items):
         if (USE_WINOGRAD_WGRAD and ks == 3 and tuple(stride) == (1, 1) and C >= WINO_WGRAD_MIN_C_BATCHED and C % 64 == 0 and K % 64 == 0 and W >= 2
                 and N * H * W * max(C, K) < 2 ** 31 and H * W * max(C, K) < 2 ** 30):
             wino.append(i)
+        elif (USE_WINOGRAD and USE_WINOGRAD_STRIDED_WGRAD and ks == 3 and wino_strided_wgrad_ok(N, H, W, C, K, stride)
+                and N * (H // 2) * (W // 32) >= WINO_STRIDED_WGRAD_MIN_CHUNKS):
+            strided.append(i)
         else:
             direct.append(i)
     out = [None] * len(items)
+    if strided:
+        for i, dw in zip(strided, _wgrad_batch_call([items[i] for i in strided], "dl_wino_strided_wgrad3x3_batch_workspace_bytes",
+                                                    "dl_wino_strided_wgrad3x3_batch_nhwc_f32", "dl_wino_strided_wgrad3x3_batch_nhwc_f32")):
+            out[i] = dw
     if wino:
         for i, dw in zip(wino, _wgrad_batch_call([items[i] for i in wino], "dl_wino_wgrad3x3_batch_workspace_bytes", "dl_wino_wgrad3x3_batch_nhwc_f32",
                                                  "dl_wino_wgrad3x3_batch_nhwc_f32")):

@@ -537,6 +537,20 @@ size_t dl_wino_wgrad3x3_batch_workspace_bytes(const dl_wgrad_layer* layers, int3
 int dl_wino_wgrad3x3_batch_nhwc_f32(const dl_wgrad_layer* layers, int32_t n, void* workspace, dl_stream stream);
 size_t dl_conv2d_wgrad_batch_workspace_bytes(const dl_wgrad_layer* layers, int32_t n);
 int dl_conv2d_wgrad_batch_nhwc_f32(const dl_wgrad_layer* layers, int32_t n, void* workspace, dl_stream stream);
+/*
+ * Weight gradients of stride-(1,2) 3x3 layers in the Winograd domain, on the pixel-pair view of dl_wino_strided_* above: x read as
+ * [N][H][W/2][2C] and g [N][H][W/2][K] are a stride-1 problem whose kernel [K][3][3][2C] has no third tap column and, for the even-pixel
+ * channels, a middle column only.  dW = G^T dU G then needs 12 of the 16 planes of dU for the odd-pixel channel blocks and 8 for the
+ * even-pixel ones: 5 C K multiply-adds per output pixel instead of the direct kernel's 9 C K.  The dead planes are neither multiplied nor
+ * transformed, accumulated or stored.  The table holds layers with ksize 3, strides (1,2); H, W, C, K describe the LAYER, dw is its own
+ * [K][3][3][C].  Slab partials are summed in a fixed order (no atomics): results are deterministic.
+ *   dl_wino_strided_wgrad_takes:  1 for stride (1,2), H even, W % 32 == 0, C and K multiples of 64, the pair view below 2^31 elements
+ *                                 (2^30 per sample); else 0.  Host only.
+ *   *_workspace_bytes:            0 when a layer is not one the query takes (dl_last_error names the field).
+ */
+int dl_wino_strided_wgrad_takes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t K, int32_t stride_h, int32_t stride_w);
+size_t dl_wino_strided_wgrad3x3_batch_workspace_bytes(const dl_wgrad_layer* layers, int32_t n);
+int dl_wino_strided_wgrad3x3_batch_nhwc_f32(const dl_wgrad_layer* layers, int32_t n, void* workspace, dl_stream stream);
 
 /*
  * The same convolutions in HALF precision (dtype DL_DTYPE_F16 or DL_DTYPE_BF16 for every activation / gradient tensor,

@@ -3,7 +3,8 @@
 //   conv_harness time [reps]      the pose CNN's layer shapes at batch 8 (64x2048 input): us, TFLOP/s, fraction of 157.3
 //   conv_harness peak             sustained fp32 MFMA rate of the whole chip (no memory traffic) and the shader clock under it
 //   conv_harness tune [reps]      the stride-1 3x3 layers with every tile variant of the tuning build
-//   conv_harness strided [reps]   the stride-(1,2) 3x3 layers: direct kernel, pixel-pair Winograd (12 planes) and its 16-plane form
+//   conv_harness strided [reps]   the stride-(1,2) 3x3 layers: direct kernel, pixel-pair Winograd (12 planes) and its 16-plane form;
+//                                 weight gradient: direct, 16 planes, live planes 12 / 8 by block (DL_SWGRAD_ALL12=1: 12 everywhere)
 // Build: make -C tools   (compiles ../delora_amd/csrc/conv.hip into the binary with -DCV_TUNE: no library needed)
 #include <hip/hip_runtime.h>
 
@@ -375,6 +376,25 @@ static void time_strided(const Shape& s, int reps, std::mt19937& gen) {
   run("pair dgrad", [&] { return dl_wino_strided_dgrad3x3_nhwc_f32(dg, ub, dgi, dag, dx, s.N, s.H, s.W, s.K, s.C, 1, 2, 1, 8 | DL_CONV_DACT, nullptr); });
   run("pair fwd 16 planes", [&] { return dl_wino_conv3x3_nhwc_f32(dx, uf, dy, nullptr, nullptr, s.N, s.H, Wo, 2 * s.C, s.K, 1, DL_CONV_ACT, nullptr, nullptr); });
   run("pair dgrad 16 planes", [&] { return dl_wino_conv3x3_nhwc_f32(dg, ub, dgi, nullptr, dx, s.N, s.H, Wo, s.K, 2 * s.C, 1, DL_CONV_DACT, nullptr, nullptr); });
+  // weight gradient (merged entry points with one layer, slab sum and output pass included): direct; the stride-1 Winograd-domain kernel on
+  // the reinterpreted shape (all 16 planes, timing only: its dW [K][3][3][2C] is the pair kernel's); live planes only -- 12 for the
+  // odd-pixel channel blocks and 8 for the even-pixel ones, or 12 for both when the process runs with DL_SWGRAD_ALL12=1
+  {
+    const char* e = getenv("DL_SWGRAD_ALL12");
+    const bool all12 = e && e[0] == '1';
+    dl_wgrad_layer L{dx, dg, nullptr, s.N, s.H, s.W, s.C, s.K, 3, 1, 2}, P{dx, dg, nullptr, s.N, s.H, Wo, 2 * s.C, s.K, 3, 1, 1};
+    const size_t b_dir = dl_conv2d_wgrad_batch_workspace_bytes(&L, 1), b_16 = dl_wino_wgrad3x3_batch_workspace_bytes(&P, 1),
+                 b_new = dl_wino_strided_wgrad3x3_batch_workspace_bytes(&L, 1);
+    float *dwo, *ws;
+    CK(hipMalloc(&dwo, 2 * nw * sizeof(float)));
+    CK(hipMalloc(&ws, std::max<size_t>(std::max(b_dir, b_16), std::max<size_t>(b_new, 4))));
+    L.dw = P.dw = dwo;
+    printf("%-26s wgrad takes: %d\n", s.name, dl_wino_strided_wgrad_takes(s.N, s.H, s.W, s.C, s.K, 1, 2));
+    run("direct wgrad", [&] { return dl_conv2d_wgrad_batch_nhwc_f32(&L, 1, ws, nullptr); });
+    run("pair wgrad 16 planes", [&] { return dl_wino_wgrad3x3_batch_nhwc_f32(&P, 1, ws, nullptr); });
+    run(all12 ? "pair wgrad 12 / 12" : "pair wgrad 12 / 8", [&] { return dl_wino_strided_wgrad3x3_batch_nhwc_f32(&L, 1, ws, nullptr); });
+    CK(hipFree(dwo)); CK(hipFree(ws));
+  }
   CK(hipFree(dx)); CK(hipFree(dw)); CK(hipFree(dg)); CK(hipFree(dag)); CK(hipFree(dy)); CK(hipFree(dgi)); CK(hipFree(uf)); CK(hipFree(ub));
 }
 
