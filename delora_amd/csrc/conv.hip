@@ -861,7 +861,7 @@ extern "C" int dl_conv2d_nhwc_f32(const float* x, const float* w, float* y, cons
   else if (ksize == 1 && stride_h == 1 && stride_w == 2) rc = dispatch_conv<GeomConv<1, 1, 2>, false, false>(a, st);
   else if (ksize == 1 && stride_h == 2 && stride_w == 2) rc = dispatch_conv<GeomConv<1, 2, 2>, false, false>(a, st);
   else return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_nhwc_f32: kernel %d stride (%d,%d) is not built", ksize, stride_h, stride_w);
-  if (rc) return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_nhwc_f32: shape N=%d H=%d W=%d C=%d K=%d does not tile (K %% %d, C %% 8)",
+  if (rc) return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_nhwc_f32: shape N=%d H=%d W=%d C=%d K=%d does not tile (K %% %d; C %% 8, most launches C %% 16: include/delora_hip.h)",
                          N, H, W, C, K, CV_BN);
   return dl_check_launch("dl_conv2d_nhwc_f32");
 }

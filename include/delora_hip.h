@@ -362,7 +362,9 @@ int dl_ring_act_pool_pad_bwd_t(const void* grad_out, const void* y, const int8_t
  *   floor((X - 1) / stride) + 1).  The IMAGE SIZE IS FREE (ABI 4): tiles hang over the right / lower edge of images that do not
  *   divide -- the reference's shipped 64x720 image has feature maps 180, 90, 45 and 23 pixels wide (config/config_datasets.yaml:21)
  *   -- odd sizes included.  Channels must tile: K % 64 == 0, C % 8 == 0 (DL_ERR_UNSUPPORTED otherwise; the caller then uses its
- *   library convolution).
+ *   library convolution).  Only the strided 3x3 layers and, below 256 channels, the stride-1 images that divide into 256-pixel tiles
+ *   (Wo % 128 == 0 with even Ho, or Wo % 64 == 0 with Ho % 4 == 0) reduce in chunks of 8 channels; every other launch needs C % 16 == 0 and refuses the
+ *   rest the same way (the Winograd entry point below takes any C % 8 == 0 on any image).
  *   ALIGNMENT (every entry point of the convolution families, fp32, Winograd and half precision alike): each tensor, weight, seam and
  *   workspace pointer must be 16-byte aligned -- operands move as 16-byte vectors (four fp32 / eight half values; the LDS DMA copies
  *   16 bytes per lane) and the channel counts above keep every pixel's row of channels a multiple of 16 bytes, so an aligned base

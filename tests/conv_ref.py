@@ -81,6 +81,16 @@ def conv_grads(x, w, g, stride=(1, 1)):
     return xr.grad.contiguous(), wr.grad.contiguous()
 
 
+def conv_dx(x_shape, w, g, stride=(1, 1)):
+    """dx [N,H,W,C] of ``conv`` alone.  A stride-1 3x3 layer's is the same convolution of g with the taps flipped and the channel
+    roles swapped (the padding is symmetric: wrap-around in W, zero rows in H) -- no autograd graph, no dw; any other layer's comes
+    from autograd with respect to x only."""
+    if w.shape[1] == 3 and tuple(stride) == (1, 1):
+        return conv(g, w.flip(1, 2).permute(3, 1, 2, 0).contiguous())
+    xr = torch.zeros(tuple(x_shape), dtype=torch.float64, requires_grad=True)      # (the map is linear: dx does not depend on x)
+    return torch.autograd.grad(conv(xr, w, stride), xr, g)[0].contiguous()
+
+
 def pool3x3s12(a):
     """Wrapped 3x3 max-pool of the stem: circular padding on W, -inf padding on H, stride (1,2).  a [N,H,W,C] -> [N,H,W/2,C]."""
     an = F.pad(_nchw(a), (1, 1, 0, 0), mode="circular")

@@ -26,6 +26,16 @@ def test_reference_equals_nested_loops(ks, stride, hw):
     assert float((g * torch.from_numpy(cr.conv_loops(x.numpy(), w2.numpy(), stride))).sum()) == float((dw * w2).sum())
 
 
+@pytest.mark.parametrize("ks,stride", GEOMS)
+def test_input_gradient_without_autograd_through_the_weights(ks, stride):
+    """``conv_dx`` (what a case without the weight-gradient pass uses) equals the dx of ``conv_grads``; the stride-1 3x3 branch is a
+    second ``conv`` with flipped, transposed taps, on an odd and an even image, one row, two columns."""
+    for H, W in ((1, 2), (3, 5), (4, 6)):
+        x, w = cr.ints((2, H, W, 3), 3, 1), cr.ints((4, ks, ks, 3), 2, 2)
+        g = cr.ints((2, cr.out_size(H, stride[0]), cr.out_size(W, stride[1]), 4), 3, 3)
+        assert torch.equal(cr.conv_dx(x.shape, w, g, stride), cr.conv_grads(x, w, g, stride)[0])
+
+
 def test_epilogue_order_and_saved_activations():
     v = torch.tensor([[-3.0, 2.0, 5.0, -1.0]], dtype=torch.float64)
     add = torch.tensor([[4.0, -4.0, 0.0, 1.0]], dtype=torch.float64)
@@ -168,6 +178,84 @@ def test_the_gpu_cases_reach_every_instantiation_at_256_cus():
     fam = {l for l in reach if l.startswith(("k_wino_conv", "k_wino_split", "k_wino_wgrad<", "k_wino_wgrad_batch<", "k_wgrad_f32<", "k_wgrad_f32_batch<", "k_wgradh<", "k_wgradh_batch<"))}
     extra = {l.replace(" one slab", "").replace(" slabs", "") for l in fam} - written
     assert not extra, sorted(extra)
+    # the persistent loop's hand-over is reached by the persistent cases and by nothing else
+    several = {l for l in written if l.endswith(cc.SEVERAL)}
+    assert len(several) == 6
+    fixed = set()
+    for c in cc.FIXED:
+        fixed |= c.labels(256)
+    assert not (fixed & several), sorted(fixed & several)
+
+
+PERSISTENT_KERNEL = {"<32,F>": "k_wino_conv<32, false, false>", "<16,F>": "k_wino_conv<16, false, false>", "<32,T>": "k_wino_conv<32, true, false>",
+                     "<16,T>": "k_wino_conv<16, true, false>", "<8,T>": "k_wino_conv<8, true, false>", "<4,T>": "k_wino_conv<4, true, false>"}
+
+
+@pytest.mark.parametrize("cu", [256, 304, 120])
+def test_persistent_cases_are_persistent_on_the_instantiation_they_name(cu):
+    """The geometries of ``persistent_cases`` were worked out by hand from wino_plan; the dispatch is the authority.  For several CU
+    counts: each case launches the instantiation its name says, forward and input gradient, with the grid capped at the CU count
+    and cu < groups < 2 cu (the "3x" ones at least 3 cu and no multiple of it)."""
+    L = _lib()
+    cases = cc.persistent_cases(cu)
+    assert set(PERSISTENT_KERNEL) < set(cases) and len(cases) == 11
+    for name, c in cases.items():
+        kernel = PERSISTENT_KERNEL[name.split(" ")[0]]
+        geom = cc.PERSISTENT_GEOMS[name if name.endswith("one image") else name.split(" ")[0]]
+        for transposed in ((False, True) if c.dgrad_ok else (False,)):
+            C, K = (c.K, c.C) if transposed else (c.C, c.K)
+            lines = L.conv_plan(L.PLAN_WINO_CONV, 0, c.N, c.H, c.W, C, K, cu_count=cu)
+            assert len(lines) == 1 and lines[0].startswith(kernel + " grid="), (name, lines)
+            groups, grid = cc.wino_groups(lines[0], c.N, c.H, c.W, K)
+            assert grid == cu and groups == c.N * geom[2] * (K // 64), (name, lines, groups)
+            handovers, block, _ = cc.block_changes(groups, grid, K // 64)
+            assert handovers == groups - grid and (block > 0) == name.endswith("several blocks"), (name, handovers, block)
+            if name.endswith("3x"):
+                assert groups >= 3 * cu and groups % cu, (name, groups)
+            else:
+                assert cu < groups < 2 * cu, (name, groups)
+        assert f"{kernel} {cc.SEVERAL}" in c.labels(cu)
+        assert (c.xmax, c.wmax) == (3, 2) and not c.wgrad_ok and c.headroom() < 2 ** 20
+    assert cases["<32,F> 72 channels"].C == 72 and not cases["<32,F> 72 channels"].dgrad_ok
+
+
+def test_persistent_cases_hand_over_inside_an_image_and_across_images():
+    """At 256 CUs a workgroup's next group is 32 positions on (the XCD swizzle): another image where an image has 2 or 3 groups,
+    the same image (other tile rows, the edge flag changing) in the 48-group geometry."""
+    cases = cc.persistent_cases(256)
+    assert cc.group_walk(cases["<32,F>"], 256) == (258, 256, 0, 2)
+    assert cc.group_walk(cases["<32,F> 3x"], 256) == (771, 256, 0, 771 - 256)
+    groups, grid, same, other = cc.group_walk(cases["<32,F> one image"], 256)
+    assert (groups, grid) == (288, 256) and same > 0 and same + other == 32
+
+
+def test_a_case_can_leave_the_weight_gradient_and_its_headroom_out():
+    assert cc.Case(86, 12, 64, 64, 64).xmax == 1                                         # the Winograd-domain weight gradient narrows it
+    with pytest.raises(AssertionError):
+        cc.Case(257, 12, 64, 64, 64, xmax=1, wmax=1).headroom()                          # ... and refuses this one outright
+    c = cc.Case(257, 12, 64, 64, 64, xmax=3, wmax=2, passes=("forward", "dgrad"))
+    assert c.dgrad_ok and not c.wgrad_ok and c.headroom() == cr.headroom("wino_conv", 64, 3, 2, add=3, dact_tanh=True)
+    L = _lib()
+    assert not any(q[0] in (L.PLAN_WGRAD, L.PLAN_WGRAD_BATCH, L.PLAN_WINO_WGRAD, L.PLAN_WINO_WGRAD_BATCH) for q in c.plan_queries())
+    fwd = cc.Case(1, 4, 64, 64, 64, passes=("forward",))
+    assert not fwd.dgrad_ok and len(fwd.plan_queries()) == 2
+
+
+def test_chunk_count_cases_and_their_split():
+    """1, 2, 3 and 9 chunks run as one range; 160 channels are 20 chunks, cut into four ranges of five (odd) at 256 CUs."""
+    L = _lib()
+    chunk = [c for c in cc.FIXED if c.dtype == cc.F32 and c.s1 and c.C in cc.CHUNK_CHANNELS]
+    assert sorted((c.H, c.W, c.C) for c in chunk) == sorted((h, w, ch) for h, w in ((4, 64), (7, 30)) for ch in cc.CHUNK_CHANNELS)
+    for c in chunk:
+        lines = L.conv_plan(L.PLAN_WINO_CONV, 0, c.N, c.H, c.W, c.C, c.K, cu_count=256)
+        kernel = ("k_wino_conv<32, false, " if c.W == 64 else "k_wino_conv<16, true, ") + ("true>" if c.C == 160 else "false>")
+        assert lines[0].startswith(kernel + " grid="), lines
+        assert lines[0].endswith(" splits=4") == (c.C == 160) and len(lines) == (2 if c.C == 160 else 1), lines
+        assert not c.dgrad_ok and not c.wgrad_ok
+    # the direct kernel reduces the ragged image in chunks of 16 channels: three cases are the Winograd kernel's alone; every
+    # case of 64-channel multiples has a direct forward by definition
+    assert [(c.W, c.C) for c in chunk if not c.direct_ok] == [(30, 8), (30, 24), (30, 72)]
+    assert all(c.direct_ok for c in cc.ALL if c not in chunk)
 
 
 # ---- arenas and the reporter (on the CPU: the helpers are device-agnostic)

@@ -60,8 +60,8 @@ def test_headroom_and_slab_plan_of_the_cases_on_the_host():
     assert min(_chunks_per_slab(lib, LONG)) >= 3
 
 
-def run_wgrad(case, dev):
-    r = Run(case, dev)
+def run_wgrad(case, dev, skew=0):
+    r = Run(case, dev, skew)
     c, lib = case, r.lib
     cr.headroom("wino_wgrad", _tiles(c), c.xmax, c.xmax)
     assert lib.dl_wino_strided_wgrad_takes(c.N, c.H, c.W, c.C, c.K, 1, 2) == 1
@@ -91,6 +91,14 @@ def test_pixel_pair_weight_gradient_equals_float64_and_the_direct_kernel(case):
     dev = _dev()
     bad = _guarded(run_wgrad, case, dev)
     util.measured(f"strided Winograd wgrad exact {case.id}: elements that differ", bad, bound=0)
+
+
+def test_minimum_documented_alignment_of_the_pixel_pair_weight_gradient():
+    """x, g, dw and the workspace 16 bytes -- the documented minimum -- past a 256-byte boundary (pair view 4x32, 128 -> 64)."""
+    dev = _dev()
+    case = cc.Case(2, 4, 2 * 32, 128, 64, 3, (1, 2), xmax=XMAX, wmax=WMAX)
+    bad = _guarded(run_wgrad, case, dev, 16)
+    util.measured(f"strided Winograd wgrad exact {case.id}, bases 16 bytes past a 256-byte boundary: elements that differ", bad, bound=0)
 
 
 def test_two_layers_in_one_launch():
