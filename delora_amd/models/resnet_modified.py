@@ -203,25 +203,26 @@ class ResNetModified(torch.nn.Module):
             # autocast: fp32 stem (8 input channels: 0.4 ms), then layer1..layer4 + pooling on the half-precision MFMA kernels
             blocks, weights = self._trunk_blocks()
             with torch.autocast("cuda", enabled=False):
+                d_ch = fc_scale = None
                 if self.dropout_active():
                     d_in, d_ch, fc_scale = self._draw_dropout(x, self.layer3[-1].conv2.out_channels)
                     x0 = ring_conv.RingStem.apply(x.float(), self.conv1.weight, ring_conv.ACT[act], d_in)
-                    return ring_conv.ring_trunk_h(x0, ring_conv.ACT[act], blocks, half, weights, channel_drop=d_ch), None, fc_scale
-                x0 = ring_conv.RingStem.apply(x.float(), self.conv1.weight, ring_conv.ACT[act])          # [N,H,W/4,C0] fp32
-                feat = ring_conv.RingTrunkH.apply(x0, ring_conv.ACT[act], blocks, half, *weights)     # [N,C'] fp32
-            return feat, None, None
+                else:
+                    x0 = ring_conv.RingStem.apply(x.float(), self.conv1.weight, ring_conv.ACT[act])      # [N,H,W/4,C0] fp32
+                feat = ring_conv.ring_trunk_h(x0, ring_conv.ACT[act], blocks, half, weights, channel_drop=d_ch)      # [N,C'] fp32
+            return feat, None, fc_scale
         if (self.hip_trunk_applicable((N, Hin, Win // 4, C0), x) and Win % 4 == 0
                 and ring_conv.planar_stem_supported(tuple(x.shape), C0)):
             # channels-last from the first layer on: stem (conv1 + act + pool) and layer1..layer4 on the HIP kernels
             blocks, weights = self._trunk_blocks()
+            d_ch = fc_scale = None
             if self.dropout_active():
                 d_in, d_ch, fc_scale = self._draw_dropout(x, self.layer3[-1].conv2.out_channels)
                 x0 = ring_conv.RingStem.apply(x, self.conv1.weight, ring_conv.ACT[act], d_in)
-                x4 = ring_conv.ring_trunk(x0, ring_conv.ACT[act], blocks, weights, channel_drop=d_ch)
-                return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), fc_scale
-            x0 = ring_conv.RingStem.apply(x, self.conv1.weight, ring_conv.ACT[act])              # [N,H,W/4,C0]
-            x4 = ring_conv.RingTrunk.apply(x0, ring_conv.ACT[act], blocks, *weights)          # [N,H',W',C']
-            return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), None
+            else:
+                x0 = ring_conv.RingStem.apply(x, self.conv1.weight, ring_conv.ACT[act])          # [N,H,W/4,C0]
+            x4 = ring_conv.ring_trunk(x0, ring_conv.ACT[act], blocks, weights, channel_drop=d_ch)       # [N,H',W',C']
+            return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), fc_scale
         return None, None, None
 
     def wide_path_dtype(self, stacked, pair=False):
@@ -253,20 +254,18 @@ class ResNetModified(torch.nn.Module):
         act = ring_conv.ACT["relu" if self.activation_fct == "relu" else "tanh"]
         blocks, weights = self._trunk_blocks()
         with torch.autocast("cuda", enabled=False):
+            d_ch = fc_scale = None
             if self.dropout_active():
                 (seed, p), d_ch, fc_scale = self._draw_dropout(stacked, self.layer3[-1].conv2.out_channels)
                 xw = ring_conv.RingTowerDrop.apply(stacked, act, seed, p, *tower_weights)   # [B,H,W,128]: dropped, channels 80.. zero
                 x0 = ring_conv.RingStemWide.apply(xw, self.conv1.weight, act, False)        # (False: the true dL/dxw goes back)
-                if dtype != torch.float32:
-                    return ring_conv.ring_trunk_h(x0, act, blocks, dtype, weights, channel_drop=d_ch), None, fc_scale
-                x4 = ring_conv.ring_trunk(x0, act, blocks, weights, channel_drop=d_ch)
-                return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), fc_scale
-            xw = ring_conv.RingTower.apply(stacked, act, False, *tower_weights)            # [B,H,W,128], channels 80.. zero
-            x0 = ring_conv.RingStemWide.apply(xw, self.conv1.weight, act, True)             # [B,H,W/4,C0]
+            else:
+                xw = ring_conv.RingTower.apply(stacked, act, False, *tower_weights)        # [B,H,W,128], channels 80.. zero
+                x0 = ring_conv.RingStemWide.apply(xw, self.conv1.weight, act, True)         # [B,H,W/4,C0]
             if dtype != torch.float32:
-                return ring_conv.RingTrunkH.apply(x0, act, blocks, dtype, *weights), None, None
-            x4 = ring_conv.RingTrunk.apply(x0, act, blocks, *weights)
-            return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), None
+                return ring_conv.ring_trunk_h(x0, act, blocks, dtype, weights, channel_drop=d_ch), None, fc_scale
+            x4 = ring_conv.ring_trunk(x0, act, blocks, weights, channel_drop=d_ch)
+            return ring_conv.MeanHW.apply(x4), x4.permute(0, 3, 1, 2), fc_scale
 
     def forward(self, x):
         act = "relu" if self.activation_fct == "relu" else "tanh"

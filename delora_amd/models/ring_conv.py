@@ -777,10 +777,8 @@ TRUNK_SEGMENTS = "mono"
 # launch keeps 128 (wgrad_nhwc): a 64-channel layer has ONE output tile, i.e. 256 slab partials of 262 KB each -- the direct kernel won.
 # Merged with the other layers of the segment it needs 64 slabs, and 2.25x fewer multiplications decide (A/B in DESIGN.md 4.6).
 WINO_WGRAD_MIN_C_BATCHED = int(os.environ.get("DELORA_WINO_WGRAD_MIN_C", "64"))
-# Weight gradients of a segment in merged launches at its end (wgrad_batch_h) instead of one launch per layer inside the chain
-WGRAD_BATCHED = os.environ.get("DELORA_WGRAD_BATCHED", "1") != "0"      # (0: one launch per layer, for A/B measurements)
-# Deferring a segment's weight gradients keeps every inter-layer GRADIENT map of the segment alive until they are computed (the
-# activations are saved tensors and alive anyway).  At B=8, 64x2048 that is ~1 GB for the 19 layers of a mono trunk; above this many
+# The weight gradients of a segment run in merged launches at its end (wgrad_batch, wgrad_batch_h).  Deferring them keeps every
+# inter-layer GRADIENT map of the segment alive until they are computed (the activations are saved tensors and alive anyway).  At B=8, 64x2048 that is ~1 GB for the 19 layers of a mono trunk; above this many
 # bytes the collected layers are flushed early (one more merged launch), so that peak memory stays bounded for large batches / tall
 # images (advisor, round 4).
 WGRAD_PENDING_MAX_BYTES = int(os.environ.get("DELORA_WGRAD_PENDING_MAX_BYTES", str(2 << 30)))
@@ -788,11 +786,10 @@ WGRAD_PENDING_MAX_BYTES = int(os.environ.get("DELORA_WGRAD_PENDING_MAX_BYTES", s
 
 class _PendingWgrads:
     """(gradient slot, (x, g, filter size, stride)) items of a segment's backward, flushed into ``grads`` through ``batch_fn`` (merged
-    launches) or ``single_fn`` at the end of the segment -- or earlier, once the gradient maps they keep alive pass
-    ``WGRAD_PENDING_MAX_BYTES``."""
+    launches) at the end of the segment -- or earlier, once the gradient maps they keep alive pass ``WGRAD_PENDING_MAX_BYTES``."""
 
-    def __init__(self, grads, meta, batch_fn, single_fn):
-        self.grads, self.meta, self.batch_fn, self.single_fn = grads, meta, batch_fn, single_fn
+    def __init__(self, grads, meta, batch_fn):
+        self.grads, self.meta, self.batch_fn = grads, meta, batch_fn
         self.items, self.bytes, self.flushes = [], 0, 0
 
     def append(self, item):
@@ -805,14 +802,12 @@ class _PendingWgrads:
     def flush(self):
         if not self.items:
             return
-        if WGRAD_BATCHED:
-            for (gi, _), dw in zip(self.items, self.batch_fn([it for _, it in self.items])):
-                self.grads[gi] = grad_for(dw, self.meta[gi])
-        else:
-            for gi, (xx, gg, ks, st) in self.items:
-                self.grads[gi] = grad_for(self.single_fn(xx, gg, ks, stride=st), self.meta[gi])
+        for (gi, _), dw in zip(self.items, self.batch_fn([it for _, it in self.items])):
+            self.grads[gi] = grad_for(dw, self.meta[gi])
         self.items, self.bytes = [], 0
         self.flushes += 1
+
+
 # Order in which the segment Functions finished their backward passes in this process (tests: DDP overlap) -- appended to when a list
 BACKWARD_TRACE = None
 
@@ -827,6 +822,174 @@ def _segments(blocks, mode):
         edges = [0] + cuts + [nb]
         return [(edges[i], edges[i + 1]) for i in range(len(edges) - 1)]
     return [(0, nb)]
+
+
+# One convolution layer of a segment as the kernel family that runs it.  Every kind answers the same two questions through the module's
+# wrappers -- ``fwd(x, act, epilogue, add)`` and the input gradient ``dgrad(g, in_hw, act, epilogue, add, dsrc, dense)`` (``add``: the
+# addend of EPI_ADD, or the grid addend of EPI_ADD_GRID; ``in_hw``: the input image, asked for only by layers of a down-sampling
+# block) -- and keeps in ``bwd`` the one tensor it wants back for ``dgrad`` (the direct kind: none), the fp32 kinds the raw
+# parameter ``w`` too.
+class _Layer:
+    def __init__(self, cin, cout, ks, stride, down, w=None, bwd=None):
+        self.cin, self.cout, self.ks, self.stride, self.down = cin, cout, ks, stride, down    # down: conv1 / 1x1 of a down-sampling block
+        self.w, self.bwd = w, bwd
+
+    def prepare(self, want_bwd):
+        """What the layer issues itself ahead of its forward launch (the batched preparations are the segment's)."""
+
+
+class _DirectLayer(_Layer):
+    """fp32 direct kernels (csrc/conv.hip) on the raw weight: ``conv_nhwc``, transposed for a stride-1 input gradient; ``dgrad_strided``
+    (one pass per stride phase, the shortcut's gradient added on the grid) for the layers of a down-sampling block."""
+
+    def prepare(self, want_bwd):
+        self.u = weight_storage(self.w)
+
+    def fwd(self, x, act=0, epilogue=0, add=None):
+        return conv_nhwc(x, self.u, stride=self.stride, act=act, epilogue=epilogue, add=add)
+
+    def dgrad(self, g, in_hw, act=0, epilogue=0, add=None, dsrc=None, dense=False):
+        if self.down:
+            return dgrad_strided(g, weight_storage(self.w), self.stride, in_hw, act=act, epilogue=epilogue, add_grid=add, dsrc=dsrc, dense=dense)
+        return conv_nhwc(g, weight_storage(self.w), act=act, epilogue=epilogue, add=add, dsrc=dsrc, transposed=True)
+
+
+class _WinoLayer(_Layer):
+    """fp32 stride-1 3x3 as fused Winograd F(2x2,3x3): ``wino_conv`` with ``u`` = u_fwd, ``bwd`` = u_bwd (``wino_weights_batch``, one
+    launch per segment).  As conv1 of a stride-1 down-sampling block its input gradient is the direct layer's, the only one that adds
+    on the grid (u_bwd is kept all the same)."""
+
+    def fwd(self, x, act=0, epilogue=0, add=None):
+        return wino_conv(x, self.u, self.cout, act=act, epilogue=epilogue, add=add)
+
+    def dgrad(self, g, in_hw, act=0, epilogue=0, add=None, dsrc=None, dense=False):
+        if self.down:
+            return _DirectLayer.dgrad(self, g, in_hw, act, epilogue, add, dsrc, dense)
+        return wino_conv(g, self.bwd, self.cin, act=act, epilogue=epilogue, add=add, dsrc=dsrc)
+
+
+class _PairLayer(_Layer):
+    """fp32 stride-(1,2) 3x3 as Winograd on the pixel-pair view: the rearranged kernel's transform is one launch of the layer's own."""
+
+    def prepare(self, want_bwd):
+        self.u, self.bwd = wino_strided_weights(self.w, self.stride, want_bwd=want_bwd)
+
+    def fwd(self, x, act=0, epilogue=0, add=None):
+        return wino_strided_conv(x, self.u, self.cout, self.stride, act=act, epilogue=epilogue)
+
+    def dgrad(self, g, in_hw, act=0, epilogue=0, add=None, dsrc=None, dense=False):
+        return wino_strided_dgrad(g, self.bwd, self.cin, self.stride, in_hw, act=act, epilogue=epilogue, add_grid=add, dsrc=dsrc)
+
+
+class _HalfLayer(_Layer):
+    """bf16 / fp16 kernels (csrc/convh.hip) on the prepared copies ``u`` = w_fwd, ``bwd`` = w_bwd (``weights_batch_h``, one launch per
+    segment); the same split between stride-1 and down-sampling layers as ``_DirectLayer``."""
+
+    def fwd(self, x, act=0, epilogue=0, add=None):
+        return conv_nhwc_h(x, self.u, self.ks, stride=self.stride, act=act, epilogue=epilogue, add=add)
+
+    def dgrad(self, g, in_hw, act=0, epilogue=0, add=None, dsrc=None, dense=False):
+        if self.down:
+            return dgrad_strided_h(g, self.bwd, self.ks, self.stride, in_hw, act=act, epilogue=epilogue, add_grid=add, dsrc=dsrc, dense=dense)
+        return conv_nhwc_h(g, self.bwd, self.ks, act=act, epilogue=epilogue, add=add, dsrc=dsrc, transposed=True)
+
+
+def _layer_plan(x_shape, blocks, dtype):
+    """The kernel family of every layer of a segment, THE routing decision: one (kind, cin, cout, filter size, stride, down) per weight
+    in weight order (conv1, conv2[, downsample]) from the input shape, the blocks, the precision and the module's switches.  fp32:
+    stride-1 3x3 layers run as Winograd when ``USE_WINOGRAD`` and ``wino_ok``; conv1 of a strided down-sampling block that
+    ``wino_strided_ok`` (``dl_wino_strided_takes``) accepts runs on the pixel-pair view (``USE_WINOGRAD_STRIDED``); every other layer,
+    the 1x1 ones included, runs the direct kernel.  Half precision has one family."""
+    plan, (N, H, W) = [], x_shape[:3]
+    half = dtype != torch.float32
+    for (cin, cout, stride, has_ds) in blocks:
+        k1 = k2 = kd = _HalfLayer if half else _DirectLayer
+        if USE_WINOGRAD and not half:
+            if stride == (1, 1):
+                k1 = _WinoLayer if wino_ok(H, W, cin, cout) else k1
+            elif USE_WINOGRAD_STRIDED and tuple(stride) != (1, 1) and has_ds and wino_strided_ok(N, H, W, cin, cout, stride):
+                k1 = _PairLayer
+        H, W = out_size(H, stride[0]), out_size(W, stride[1])
+        if USE_WINOGRAD and not half and wino_ok(H, W, cout, cout):
+            k2 = _WinoLayer
+        plan += [(k1, cin, cout, 3, stride, has_ds), (k2, cout, cout, 3, (1, 1), False)]
+        if has_ds:
+            plan.append((kd, cin, cout, 1, stride, True))
+    return plan
+
+
+def _segment_forward(ctx, plan, layers, x0, act, blocks, first, last, need_bwd, keep):
+    """The forward walk of both precisions: per block conv1, shortcut, conv2 on ``layers`` (``plan`` made into objects, the batched
+    weight preparations attached).  Saved for the backward pass: x0 and the two activations per block, ``keep`` (fp32: the raw
+    weights), the layers' ``bwd`` tensors, the tensor ``first``; ``ctx`` itself holds no tensor."""
+    saved, x, it = [x0], x0, iter(layers)
+    for (_, _, _, has_ds) in blocks:
+        l1, l2 = next(it), next(it)
+        if has_ds:                                      # (the 1x1 weight's view is taken ahead of conv1: tests pin the call order)
+            ld = next(it)
+            ld.prepare(need_bwd)
+        l1.prepare(need_bwd)
+        y1 = l1.fwd(x, act, EPI_ACT)
+        shortcut = ld.fwd(x) if has_ds else x
+        l2.prepare(need_bwd)
+        x = l2.fwd(y1, act, EPI_ADD | EPI_ACT, shortcut)
+        saved += [y1, x]
+    dsrc0 = [first] if torch.is_tensor(first) else []
+    ctx.act, ctx.blocks, ctx.first, ctx.last, ctx.plan, ctx.has_dsrc0 = act, blocks, not dsrc0 and bool(first), last, plan, bool(dsrc0)
+    ctx.save_for_backward(*saved, *keep, *[l.bwd for l in layers if l.bwd is not None], *dsrc0)
+    return x
+
+
+def _saved(ctx):
+    """What ``_segment_forward`` saved: (x0 and the two activations per block, the Function's own tensors, the tensor ``first`` or None)."""
+    saved, n = ctx.saved_tensors, 1 + 2 * len(ctx.blocks)
+    if ctx.has_dsrc0:
+        return saved[:n], saved[n:-1], saved[-1]
+    return saved[:n], saved[n:], None
+
+
+def _segment_backward(ctx, layers, acts, dsrc0, dy, meta, batch_fn):
+    """The backward walk of both precisions on the rebuilt ``layers``: the chain of input gradients, act' and the shortcut's gradient in
+    their epilogues; ``meta``: what ``grad_for`` lays the weight gradients of ``batch_fn`` out by."""
+    act, blocks = ctx.act, ctx.blocks
+    nb = len(blocks)
+    grads = [None] * len(layers)
+    g2 = dy.contiguous()
+    if ctx.last:                                        # a true dL/dy: the activation derivative is applied here
+        y_last = acts[-1]
+        if act == ACT["tanh"] and g2.dtype == torch.float32:
+            g2 = g2 * (1.0 - y_last * y_last)
+        elif act == ACT["tanh"]:                        # half precision: in fp32, one rounding (never taken by ring_trunk_h, whose
+            g2 = (g2.float() * (1.0 - y_last.float() ** 2)).to(g2.dtype)      # pooling hands over the pre-activation gradient)
+        elif act == ACT["relu"]:
+            g2 = g2 * (y_last > 0).to(g2.dtype)
+    # The weight gradients do not feed the chain of input gradients: they are collected (x, g stay alive) and computed together at
+    # the end of the segment -- merged launches need far fewer slab partials than one launch per layer (wgrad_batch, wgrad_batch_h)
+    pending = _PendingWgrads(grads, meta, batch_fn)
+    wi = len(layers)
+    for b in range(nb - 1, -1, -1):
+        stride, has_ds = blocks[b][2], blocks[b][3]
+        wi -= 3 if has_ds else 2
+        l1, l2 = layers[wi], layers[wi + 1]
+        x, y1 = acts[2 * b], acts[2 * b + 1]
+        # x0 of the first segment is the pooled stem output: its act' belongs to the stem.  Elsewhere the returned gradient carries
+        # act' of x -- or of the map x0 was scaled from (``first`` as a tensor)
+        dsrc = None if ctx.first and b == 0 else dsrc0 if b == 0 and dsrc0 is not None else x
+        dact = EPI_DACT if dsrc is not None else 0
+        pending.append((wi + 1, (y1, g2, 3, (1, 1))))
+        g1 = l2.dgrad(g2, None, act, EPI_DACT, None, y1)
+        pending.append((wi, (x, g1, 3, stride)))
+        if not has_ds:
+            g2 = l1.dgrad(g1, None, act, EPI_ADD | dact, g2, dsrc)
+        else:
+            pending.append((wi + 2, (x, g2, 1, stride)))
+            # down-sampling branch on the grid, then one pass per stride phase of the 3x3 layer with it and act'(x) fused
+            dxb = layers[wi + 2].dgrad(g2, x.shape[1:3], dense=True)
+            g2 = l1.dgrad(g1, x.shape[1:3], act, EPI_ADD_GRID | dact, dxb, dsrc)
+    pending.flush()
+    if BACKWARD_TRACE is not None:
+        BACKWARD_TRACE.append(("segment", blocks[0][0], blocks[-1][1], nb))
+    return (g2, None, None, None, None, *grads)
 
 
 class RingSegment(torch.autograd.Function):
@@ -845,120 +1008,24 @@ class RingSegment(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, act, blocks, first, last, *weights):
-        """Stride-1 3x3 layers run as fused Winograd F(2x2,3x3) when ``USE_WINOGRAD`` and the shape tiles (their
-        Winograd-domain weights for the backward pass are produced by the same launch and kept for it); stride-(1,2) 3x3 layers
-        that ``dl_wino_strided_takes`` accepts run on the same kernel through the pixel-pair view (``USE_WINOGRAD_STRIDED``); the
-        other strided layers and the 1x1 layers run the direct kernel."""
-        saved, x, wi = [x0], x0, 0
-        ubwd = []
+        """Which kernel runs which layer is ``_layer_plan``'s decision.  The Winograd-domain weights of the stride-1 layers, those for
+        the backward pass included, come from one launch for the segment."""
         need_bwd = any(ctx.needs_input_grad)
-        # which layers of this segment run as Winograd (shape walk), and their transformed weights in ONE launch
-        plan, (N, H, W) = [], x0.shape[:3]
-        for (cin, cout, stride, has_ds) in blocks:
-            use1 = USE_WINOGRAD and stride == (1, 1) and wino_ok(H, W, cin, cout)
-            if USE_WINOGRAD and USE_WINOGRAD_STRIDED and tuple(stride) != (1, 1) and has_ds and wino_strided_ok(N, H, W, cin, cout, stride):
-                use1 = "strided"
-            H, W = out_size(H, stride[0]), out_size(W, stride[1])
-            use2 = USE_WINOGRAD and wino_ok(H, W, cout, cout)
-            plan.append((use1, use2))
-        wlist, wj = [], 0
-        for (cin, cout, stride, has_ds), (use1, use2) in zip(blocks, plan):
-            if use1 is True:
-                wlist.append(weights[wj])
-            if use2:
-                wlist.append(weights[wj + 1])
-            wj += 3 if has_ds else 2
-        us = iter(wino_weights_batch(wlist, want_bwd=need_bwd))
-        for (cin, cout, stride, has_ds), (use1, use2) in zip(blocks, plan):
-            w1p, w2p = weights[wi], weights[wi + 1]
-            wd = weight_storage(weights[wi + 2]) if has_ds else None
-            wi += 3 if has_ds else 2
-            if use1 == "strided":                            # the rearranged kernel's transform: one launch more per strided layer
-                uf, ub1 = wino_strided_weights(w1p, stride, want_bwd=need_bwd)
-                y1 = wino_strided_conv(x, uf, cout, stride, act=act, epilogue=EPI_ACT)
-            elif use1:
-                uf, ub1 = next(us)
-                y1 = wino_conv(x, uf, cout, act=act, epilogue=EPI_ACT)
-            else:
-                ub1 = None
-                y1 = conv_nhwc(x, weight_storage(w1p), stride=stride, act=act, epilogue=EPI_ACT)
-            shortcut = conv_nhwc(x, wd, stride=stride) if has_ds else x
-            if use2:
-                uf, ub2 = next(us)
-                y2 = wino_conv(y1, uf, cout, act=act, epilogue=EPI_ADD | EPI_ACT, add=shortcut)
-            else:
-                ub2 = None
-                y2 = conv_nhwc(y1, weight_storage(w2p), act=act, epilogue=EPI_ADD | EPI_ACT, add=shortcut)
-            ubwd += [ub1, ub2]
-            saved += [y1, y2]
-            x = y2
-        dsrc0 = first if torch.is_tensor(first) else None
-        ctx.act, ctx.blocks, ctx.first, ctx.last = act, blocks, dsrc0 is None and bool(first), last
+        plan = _layer_plan(x0.shape, blocks, torch.float32)
+        layers = [kind(*shape, w) for (kind, *shape), w in zip(plan, weights)]
+        wino = [l for l in layers if type(l) is _WinoLayer]            # their transformed weights in ONE launch
+        for l, u in zip(wino, wino_weights_batch([l.w for l in wino], want_bwd=need_bwd)):
+            l.u, l.bwd = u
         # the Winograd-domain backward weights travel with the saved tensors (released with the graph, covered by autograd's
         # in-place version check like the raw weights); layers on the direct kernel have none
-        ctx.ubwd_mask = tuple(u is not None for u in ubwd)
-        ctx.has_dsrc0 = dsrc0 is not None
-        ctx.save_for_backward(*saved, *weights, *[u for u in ubwd if u is not None], *([dsrc0] if dsrc0 is not None else []))
-        return x
+        return _segment_forward(ctx, plan, layers, x0, act, blocks, first, last, need_bwd, weights)
 
     @staticmethod
     def backward(ctx, dy):
-        act, blocks = ctx.act, ctx.blocks
-        nb = len(blocks)
-        saved = ctx.saved_tensors
-        dsrc0 = None
-        if ctx.has_dsrc0:
-            saved, dsrc0 = saved[:-1], saved[-1]
-        nu = sum(ctx.ubwd_mask)
-        acts, weights = saved[:1 + 2 * nb], saved[1 + 2 * nb:len(saved) - nu]
-        u_it = iter(saved[len(saved) - nu:])
-        ubwd = [next(u_it) if has else None for has in ctx.ubwd_mask]
-        grads = [None] * len(weights)
-        g2 = dy.contiguous()
-        if ctx.last:                                        # a true dL/dy: the activation derivative is applied here
-            y_last = acts[-1]
-            if act == ACT["tanh"]:
-                g2 = g2 * (1.0 - y_last * y_last)
-            elif act == ACT["relu"]:
-                g2 = g2 * (y_last > 0).to(g2.dtype)
-        wi = len(weights)
-        # The weight gradients do not feed the chain of input gradients: they are collected (x, g stay alive) and computed together at
-        # the end of the segment -- merged launches need far fewer slab partials than one launch per layer (wgrad_batch)
-        pending = _PendingWgrads(grads, weights, wgrad_batch, wgrad_nhwc)
-        for b in range(nb - 1, -1, -1):
-            cin, cout, stride, has_ds = blocks[b]
-            wi -= 3 if has_ds else 2
-            w1p, w2p = weights[wi], weights[wi + 1]
-            x, y1 = acts[2 * b], acts[2 * b + 1]
-            first = ctx.first and b == 0                    # x0 is the pooled stem output: its act' belongs to the stem
-            xd = dsrc0 if (b == 0 and dsrc0 is not None) else x      # the map whose act' the returned gradient carries
-            pending.append((wi + 1, (y1, g2, 3, (1, 1))))
-            ub1, ub2 = ubwd[2 * b], ubwd[2 * b + 1]
-            if ub2 is not None:
-                g1 = wino_conv(g2, ub2, cout, act=act, epilogue=EPI_DACT, dsrc=y1)
-            else:
-                g1 = conv_nhwc(g2, weight_storage(w2p), act=act, epilogue=EPI_DACT, dsrc=y1, transposed=True)
-            pending.append((wi, (x, g1, 3, stride)))
-            if not has_ds:
-                epi = EPI_ADD if first else (EPI_ADD | EPI_DACT)
-                if ub1 is not None:
-                    g2 = wino_conv(g1, ub1, cin, act=act, epilogue=epi, add=g2, dsrc=None if first else xd)
-                else:
-                    g2 = conv_nhwc(g1, weight_storage(w1p), act=act, epilogue=epi, add=g2, dsrc=None if first else xd, transposed=True)
-            else:
-                wdp = weights[wi + 2]
-                pending.append((wi + 2, (x, g2, 1, stride)))
-                # down-sampling branch on the grid, then one pass per stride phase of the 3x3 layer with it and act'(x) fused
-                dxb = dgrad_strided(g2, weight_storage(wdp), stride, x.shape[1:3], dense=True)
-                epi = EPI_ADD_GRID if first else (EPI_ADD_GRID | EPI_DACT)
-                if ub1 is not None and tuple(stride) != (1, 1):       # (pixel-pair Winograd: forward took the layer)
-                    g2 = wino_strided_dgrad(g1, ub1, cin, stride, x.shape[1:3], act=act, epilogue=epi, add_grid=dxb, dsrc=None if first else xd)
-                else:
-                    g2 = dgrad_strided(g1, weight_storage(w1p), stride, x.shape[1:3], act=act, epilogue=epi, add_grid=dxb, dsrc=None if first else xd)
-        pending.flush()
-        if BACKWARD_TRACE is not None:
-            BACKWARD_TRACE.append(("segment", blocks[0][0], blocks[-1][1], nb))
-        return (g2, None, None, None, None, *grads)
+        acts, rest, dsrc0 = _saved(ctx)                 # rest: the raw weights, then u_bwd of the layers that have one
+        u_bwd = iter(rest[len(ctx.plan):])
+        layers = [kind(*shape, w, None if kind is _DirectLayer else next(u_bwd)) for (kind, *shape), w in zip(ctx.plan, rest)]
+        return _segment_backward(ctx, layers, acts, dsrc0, dy, rest[:len(layers)], wgrad_batch)
 
 
 def _run_segments(fn, x, act, blocks, weights, mode, last_applies_act, channel_drop=None):
@@ -1122,71 +1189,19 @@ class RingSegmentH(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, act, blocks, first, last, *weights):
-        dtype = x0.dtype
         need_bwd = any(ctx.needs_input_grad)
-        saved, wbs, x, wi = [x0], [], x0, 0
-        prepared = weights_batch_h(list(weights), dtype, want_bwd=need_bwd)        # every convolution of the segment: one launch
-        for (cin, cout, stride, has_ds) in blocks:
-            (w1f, w1b), (w2f, w2b) = prepared[wi], prepared[wi + 1]
-            wdf, wdb = prepared[wi + 2] if has_ds else (None, None)
-            wi += 3 if has_ds else 2
-            y1 = conv_nhwc_h(x, w1f, 3, stride=stride, act=act, epilogue=EPI_ACT)
-            shortcut = conv_nhwc_h(x, wdf, 1, stride=stride) if has_ds else x
-            y2 = conv_nhwc_h(y1, w2f, 3, act=act, epilogue=EPI_ADD | EPI_ACT, add=shortcut)
-            wbs += [w1b, w2b] + ([wdb] if has_ds else [])
-            saved += [y1, y2]
-            x = y2
-        dsrc0 = first if torch.is_tensor(first) else None           # see RingSegment
-        ctx.act, ctx.blocks, ctx.first, ctx.last = act, blocks, dsrc0 is None and bool(first), last
-        ctx.n_w = len(weights)
+        plan = _layer_plan(x0.shape, blocks, x0.dtype)
+        layers = [kind(*shape) for kind, *shape in plan]
+        for l, w in zip(layers, weights_batch_h(list(weights), x0.dtype, want_bwd=need_bwd)):      # every convolution of the segment: one launch
+            l.u, l.bwd = w
         ctx.w_meta = [(tuple(w.shape), tuple(w.stride())) for w in weights]
-        ctx.has_dsrc0 = dsrc0 is not None
-        ctx.save_for_backward(*saved, *(wbs if need_bwd else []), *([dsrc0] if dsrc0 is not None else []))
-        return x
+        return _segment_forward(ctx, plan, layers, x0, act, blocks, first, last, need_bwd, ())
 
     @staticmethod
     def backward(ctx, dy):
-        act, blocks = ctx.act, ctx.blocks
-        nb = len(blocks)
-        saved = ctx.saved_tensors
-        dsrc0 = None
-        if ctx.has_dsrc0:
-            saved, dsrc0 = saved[:-1], saved[-1]
-        acts, wbs = saved[:1 + 2 * nb], saved[1 + 2 * nb:]
-        grads = [None] * ctx.n_w
-        g2 = dy.contiguous()
-        if ctx.last:                                    # never taken by ring_trunk_h (the pooling Function hands over the pre-
-            y_last = acts[-1]                           # activation gradient); kept for stand-alone use of a segment
-            if act == ACT["tanh"]:
-                g2 = (g2.float() * (1.0 - y_last.float() ** 2)).to(g2.dtype)
-            elif act == ACT["relu"]:
-                g2 = g2 * (y_last > 0).to(g2.dtype)
-        wi = ctx.n_w
-        # The weight gradients do not feed the chain of input gradients: they are collected (x, g kept alive) and computed together
-        # at the end of the segment -- merged launches need far fewer slab partials than one launch per layer (wgrad_batch_h)
-        pending = _PendingWgrads(grads, ctx.w_meta, wgrad_batch_h, wgrad_nhwc_h)
-        for b in range(nb - 1, -1, -1):
-            cin, cout, stride, has_ds = blocks[b]
-            wi -= 3 if has_ds else 2
-            w1b, w2b = wbs[wi], wbs[wi + 1]
-            x, y1 = acts[2 * b], acts[2 * b + 1]
-            first = ctx.first and b == 0
-            xd = dsrc0 if (b == 0 and dsrc0 is not None) else x
-            pending.append((wi + 1, (y1, g2, 3, (1, 1))))
-            g1 = conv_nhwc_h(g2, w2b, 3, act=act, epilogue=EPI_DACT, dsrc=y1, transposed=True)
-            pending.append((wi, (x, g1, 3, stride)))
-            if not has_ds:
-                epi = EPI_ADD if first else (EPI_ADD | EPI_DACT)
-                g2 = conv_nhwc_h(g1, w1b, 3, act=act, epilogue=epi, add=g2, dsrc=None if first else xd, transposed=True)
-            else:
-                pending.append((wi + 2, (x, g2, 1, stride)))
-                dxb = dgrad_strided_h(g2, wbs[wi + 2], 1, stride, x.shape[1:3], dense=True)
-                epi = EPI_ADD_GRID if first else (EPI_ADD_GRID | EPI_DACT)
-                g2 = dgrad_strided_h(g1, w1b, 3, stride, x.shape[1:3], act=act, epilogue=epi, add_grid=dxb, dsrc=None if first else xd)
-        pending.flush()
-        if BACKWARD_TRACE is not None:
-            BACKWARD_TRACE.append(("segment", blocks[0][0], blocks[-1][1], nb))
-        return (g2, None, None, None, None, *grads)
+        acts, w_bwd, dsrc0 = _saved(ctx)
+        layers = [kind(*shape, None, w) for (kind, *shape), w in zip(ctx.plan, w_bwd)]
+        return _segment_backward(ctx, layers, acts, dsrc0, dy, ctx.w_meta, wgrad_batch_h)
 
 
 class MeanHWActH(torch.autograd.Function):
