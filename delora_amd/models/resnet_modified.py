@@ -6,7 +6,8 @@ tanh (or relu) activations, every 3x3 convolution sees one wrapped column on eac
 each side of H, strides (1,2) in the stem/pool/layer2/layer3 and (2,2) in layer4.
 
 Two GPU paths compute it (``cnn_impl``; both are compared with each other and with torch-CPU in the tests):
-  * fp32 tensors on shapes that tile (the reference's full-size network on 64/128-ring images): three autograd
+  * fp32 tensors on shapes that tile (the reference's full-size network on 64/128-ring images, and the narrow networks of
+    ``factor_fewer_resnet_channels`` 2 and 4, whose layers below 64 channels run on the narrow MFMA family, csrc/narrow.hip): three autograd
     Functions on channels-last activations -- ``ring_conv.RingStem`` (conv1 + activation + max-pooling), ``RingSegment``
     for layer1..layer4 (fused Winograd / direct MFMA convolutions with the wrap-around as addressing and the elementwise tail
     in their epilogues; one Function in a single process, cut per layer under DDP so that the gradient all-reduce overlaps
@@ -14,7 +15,8 @@ Two GPU paths compute it (``cnn_impl``; both are compared with each other and wi
     (``RingSegmentH``: csrc/convh.hip, wgradh.hip).  ``use_dropout`` in training mode stays on this path: the input mask is applied
     inside the stem's transposing copy, the channel mask by ``ring_conv.ChannelDropout`` at an extra cut in front of layer4, the
     fc mask inside the fused heads (csrc/dropout.hip: a counter-based stream of the library's own, seeded per forward pass);
-  * everything else (narrow test networks, autocast shapes that do not tile, ``cnn_impl: modules``): the modules below -- library convolutions on inputs that
+  * everything else (factor 8, narrow networks under autocast or behind the feature tower, widths that are not multiples of 4,
+    ``cnn_impl: modules``): the modules below -- library convolutions on inputs that
     travel in wrapped form, with activation (+ residual add) and the wrap-around padding as ONE fused HIP elementwise op
     (``ring_ops.ring_act_pad``) instead of the reference's separate tanh, add and three-copy F.pad per layer, and the
     stem's activation + padding + max-pooling + padding as one more (``ring_ops.ring_act_pool_pad``).
@@ -122,7 +124,7 @@ class ResNetModified(torch.nn.Module):
 
     def _note_module_path(self, x, why=None):
         """One line per (shape, dtype, mode) whenever a CUDA input takes the module path (library convolutions + ring ops) instead of
-        the HIP stem + trunk: a 5x slower path must not be taken silently (narrow test networks, widths not divisible by 4).
+        the HIP stem + trunk: a 5x slower path must not be taken silently (factor-8 networks, widths not divisible by 4).
         ``why``: the caller's own reason (the feature tower in front of this network, models/model.py)."""
         if not x.is_cuda or self.impl == "modules":
             return
@@ -131,7 +133,8 @@ class ResNetModified(torch.nn.Module):
         if key not in seen:
             seen.add(key)
             why = why or ("autocast shapes do not tile (csrc/convh.hip)" if key[2]
-                          else "channel counts are not multiples of 64, or the width is not a multiple of 4"
+                          else "channel counts are neither multiples of 64 nor a narrow network's 16 / 32 (factor_fewer_resnet_channels 2 and 4 "
+                          "of an 8-channel input), or the width is not a multiple of 4"
                           + (" (with dropout the HIP stem has to take the input as well as the trunk)" if key[3] else ""))
             print(f"[delora_amd] CNN input {key[0]} {str(x.dtype).replace('torch.', '')} runs on the MODULE path (library convolutions), "
                   f"not on the HIP stem + trunk: {why}", flush=True)
@@ -139,7 +142,7 @@ class ResNetModified(torch.nn.Module):
     def hip_path_takes(self, H, W, in_channels=None, batch=1):
         """Whether an ``[N,in_channels,H,W]`` fp32 CUDA input (default: this network's own input channels -- 8, or the feature
         tower's 80) would run on the channels-last HIP stem + trunk (shape test only: ``ring_conv.supported`` / ``stem_supported``:
-        full-width channel counts, a width divisible by 4).  True for BASELINE's
+        full-width channel counts or those of factor_fewer_resnet_channels 2 and 4 on the 8-channel input, a width divisible by 4).  True for BASELINE's
         images and for the reference's shipped 64 x 720 and 64 x 512 (tiles hang over the edges of maps that do not divide)."""
         if self.impl == "modules" or W % 4:
             return False
@@ -149,13 +152,14 @@ class ResNetModified(torch.nn.Module):
         if in_channels == ring_conv.TOWER_CHANNELS and not ring_conv.tower_supported((batch, 8, H, W)):
             return False
         return (ring_conv.stem_supported((batch, in_channels, H, W), C0)
-                and ring_conv.supported((batch, H, W // 4, C0), self._trunk_blocks()[0]))
+                and ring_conv.supported((batch, H, W // 4, C0), self._trunk_blocks()[0], narrow=in_channels == 8))
 
-    def hip_trunk_applicable(self, x_pooled_shape_nhwc, x):
-        """The HIP trunk runs fp32 CUDA tensors outside autocast on shapes that tile (with or without dropout)."""
+    def hip_trunk_applicable(self, x_pooled_shape_nhwc, x, narrow=True):
+        """The HIP trunk runs fp32 CUDA tensors outside autocast on shapes that tile (with or without dropout): channel counts multiples
+        of 64, or -- ``narrow`` -- a narrow network's (``ring_conv.supported``)."""
         if self.impl == "modules" or not x.is_cuda or x.dtype != torch.float32 or torch.is_autocast_enabled():
             return False
-        return ring_conv.supported(x_pooled_shape_nhwc, self._trunk_blocks()[0])
+        return ring_conv.supported(x_pooled_shape_nhwc, self._trunk_blocks()[0], narrow=narrow)
 
     def hip_half_applicable(self, x):
         """The half-precision HIP trunk (``ring_conv.RingTrunkH``) runs CUDA inputs inside ``torch.autocast`` (fp16 / bf16) on shapes
@@ -282,7 +286,9 @@ class ResNetModified(torch.nn.Module):
         p = ring_act_pad(x, "none", pad=True)
         p = ring_act_pool_pad(self.conv1(p), act)                    # act + wrap + self.maxpool + wrap, fused
         N, C0, H0, Wp = p.shape
-        if not self.dropout_active() and self.hip_trunk_applicable((N, H0, Wp - 2, C0), p):
+        # (a narrow network gets here only with an input the HIP stem refuses -- the feature tower's 80 channels, a width that is not a
+        # multiple of 4: it stays on the module path as a whole)
+        if not self.dropout_active() and self.hip_trunk_applicable((N, H0, Wp - 2, C0), p, narrow=False):
             # channels-last trunk: layer1..layer4 as one autograd Function on the fp32 matrix cores
             blocks, weights = self._trunk_blocks()
             if Cin == ring_conv.TOWER_CHANNELS:        # behind the feature tower: tower and stem ran as library convolutions

@@ -170,11 +170,16 @@ def wgrad_batch(items):
     (x, g, ks, stride); returns ``dW [K,k,k,C]`` per item.  Stride-1 3x3 layers with at least 128 input channels take the Winograd-domain
     kernel (as ``wgrad_nhwc`` decides), stride-(1,2) 3x3 layers that ``wino_strided_wgrad_ok`` takes and that are large enough the
     pixel-pair form of it (``USE_WINOGRAD_STRIDED_WGRAD``), the rest the direct one; within each family the layers that share a kernel run in ONE launch
-    with far fewer pixel slabs (fp32 partial copies of the gradient) per layer than a launch of their own needs."""
+    with far fewer pixel slabs (fp32 partial copies of the gradient) per layer than a launch of their own needs.  A narrow network's layers
+    (fewer than 64 channels on a side) are not merged: each takes the narrow family's launch pair (``narrow_wgrad``)."""
     wino, strided, direct = [], [], []
+    out = [None] * len(items)
     for i, (x, g, ks, stride) in enumerate(items):
         N, H, W, C = x.shape
         K = g.shape[3]
+        if C % 64 or K % 64:                           # a narrow network's layer: a launch pair of its own (csrc/narrow.hip)
+            out[i] = narrow_wgrad(x, g, ks, stride)
+            continue
         # (the shape rule of dl_wino_wgrad_workspace_bytes, restated here: one library call per layer and step is host time)
         if (USE_WINOGRAD_WGRAD and ks == 3 and tuple(stride) == (1, 1) and C >= WINO_WGRAD_MIN_C_BATCHED and C % 64 == 0 and K % 64 == 0 and W >= 2
                 and N * H * W * max(C, K) < 2 ** 31 and H * W * max(C, K) < 2 ** 30):
@@ -184,7 +189,6 @@ def wgrad_batch(items):
             strided.append(i)
         else:
             direct.append(i)
-    out = [None] * len(items)
     if strided:
         for i, dw in zip(strided, _wgrad_batch_call([items[i] for i in strided], "dl_wino_strided_wgrad3x3_batch_workspace_bytes",
                                                     "dl_wino_strided_wgrad3x3_batch_nhwc_f32", "dl_wino_strided_wgrad3x3_batch_nhwc_f32")):
@@ -311,24 +315,34 @@ def wino_strided_dgrad(g, u_bwd, C, stride, in_hw, act=0, epilogue=0, add_grid=N
     return dx
 
 
-def supported(x_shape, blocks):
-    """Whether the HIP trunk can run these shapes: channel counts multiples of 64.  The image size is free: tiles hang over the edge
+def supported(x_shape, blocks, narrow=False):
+    """Whether the fp32 HIP trunk can run these shapes: channel counts multiples of 64, or, with ``narrow`` -- the first layers of a narrow
+    network (``factor_fewer_resnet_channels`` 2 and 4), asked for by the 8-channel pose network alone -- multiples of 16 inside the narrow
+    family's domain at stride (1,1) / (1,2).  The image size is free: tiles hang over the edge
     of feature maps that do not divide, odd widths / heights included -- the reference's shipped 64x720 image (feature maps 180, 90,
     45 and 23 pixels wide, config/config_datasets.yaml:21) and 64x512 (layer4: 32x16, :47) run here like BASELINE's 64x2048."""
-    return _supported(x_shape, blocks, 1 << 31)
+    return _supported(x_shape, blocks, 1 << 31, narrow=narrow)
 
 
-def _supported(x_shape, blocks, max_elements):
+def _channels_tile(c, narrow):
+    return c % 64 == 0 or (narrow and c % 16 == 0 and narrow_ok(c, c))
+
+
+def _supported(x_shape, blocks, max_elements, narrow=False):
     """``max_elements``: the C side indexes a tensor with 32-bit element (fp32) / byte (half) offsets and rejects N*H*W*max(C,K) at or
     above 2^31 (conv.hip, wino.hip) resp. 2^30 (convh.hip, wgradh.hip); the Winograd kernels additionally keep a sample's H*W*C below
-    2^30.  The same bounds here let cnn_impl 'auto' fall back to the module path instead of raising from the C side."""
+    2^30.  The same bounds here let cnn_impl 'auto' fall back to the module path instead of raising from the C side.  ``narrow``: 16,
+    32 and 48 channels count as well (fp32 only: csrc/narrow.hip), at the strides that family has."""
     N, H, W, C = x_shape
-    if C % 64 or H < 1 or W < 1:
+    if not _channels_tile(C, narrow) or H < 1 or W < 1:
         return False
     for (cin, cout, stride, _) in blocks:
-        if cin % 64 or cout % 64 or stride[0] not in (1, 2) or stride[1] not in (1, 2) or (stride[0] == 2 and stride[1] == 1):
+        if (not _channels_tile(cin, narrow) or not _channels_tile(cout, narrow) or stride[0] not in (1, 2) or stride[1] not in (1, 2)
+                or (stride[0] == 2 and stride[1] == 1)):
             return False
-        wide = max(cin, cout)
+        if (cin % 64 or cout % 64) and (stride[0] != 1 or not narrow_ok(cin, cout)):
+            return False
+        wide = max(cin, cout, 64 if (cin % 64 or cout % 64) else 0)         # (the narrow family bounds N*H*W*64)
         if N * H * W * wide >= max_elements or H * W * wide >= (1 << 30):
             return False
         H, W = out_size(H, stride[0]), out_size(W, stride[1])
@@ -496,13 +510,16 @@ def channel_scale(x, scale):
 
 TOWER_CHANNELS = 80          # stem input behind the per-image feature tower: 2 x 40 channels
 TOWER_PITCH = 128            # ... held in a [N,H,W,128] buffer whose channels 80..127 are zero (``RingStemWide``)
+NARROW_STEM_CHANNELS = (16, 32)      # conv1 outputs of factor_fewer_resnet_channels 4 and 2 (factor 8 stays on the module path)
 
 
 def stem_supported(x_shape, out_channels):
     """Whether the HIP stem takes an input ``[N,C,H,W]``: ``RingStem`` for 8 input channels per chunk, ``RingStemWide`` for the 80
-    channels of the feature tower; 64-channel output tiles, a width that halves twice."""
+    channels of the feature tower; 64-channel output tiles -- or, for the 8-channel planar stem alone, the 16 / 32 output channels of a
+    narrow network (conv1 on csrc/narrow.hip) --, a width that halves twice."""
     N, C, H, W = x_shape
-    return ((C % 8 == 0 and C % 16 != 0) or C == TOWER_CHANNELS) and out_channels % 64 == 0 and W % 4 == 0 and W >= 4 and H >= 1
+    k_ok = out_channels % 64 == 0 or (C == 8 and out_channels in NARROW_STEM_CHANNELS and N * H * W * 64 < (1 << 31))
+    return ((C % 8 == 0 and C % 16 != 0) or C == TOWER_CHANNELS) and k_ok and W % 4 == 0 and W >= 4 and H >= 1
 
 
 def planar_stem_supported(x_shape, out_channels):
@@ -516,7 +533,9 @@ class RingStem(torch.autograd.Function):
     one transposing copy of the 8-channel input, the direct MFMA convolution with the activation in its epilogue, the
     pooling kernel.  Backward: pooling backward + activation derivative + conv1's weight gradient in ONE kernel
     (``dl_stem_wgrad_f32``); only when the gradient with respect to the INPUT image is wanted (never in training: the range image
-    is data) the three steps run separately with the library's convolution backward.  The 134 MB pre-pooling map is kept for
+    is data) the three steps run separately with the library's convolution backward.  A narrow network's conv1 (16 / 32 output
+    channels) runs on the narrow family (``narrow_conv``); its backward is the pooling backward + the strided ``narrow_wgrad``, two
+    launches and a slab sum instead of the fused kernel, which stays the 64-channel path.  The 134 MB pre-pooling map is kept for
     the backward (the pooled output is not: the trunk saves it).
 
     An optional fourth argument ``drop = (seed, p)`` applies the element-wise input dropout (site 1 of csrc/dropout.hip) inside the
@@ -533,7 +552,8 @@ class RingStem(torch.autograd.Function):
             seed = None
             x8 = x.permute(0, 2, 3, 1).contiguous()
         ctx.n_extra = len(drop)
-        a = conv_nhwc(x8, weight_storage(w1), stride=(1, 2), act=act, epilogue=EPI_ACT if act else 0)
+        conv1 = conv_nhwc if w1.shape[0] % 64 == 0 else narrow_conv          # (a narrow network's 16 / 32 output channels)
+        a = conv1(x8, weight_storage(w1), stride=(1, 2), act=act, epilogue=EPI_ACT if act else 0)
         y, win = pool_fwd(a)
         ctx.save_for_backward(x8, a, win, w1, *([seed] if seed is not None else []))
         ctx.act = act
@@ -556,6 +576,10 @@ class RingStem(torch.autograd.Function):
                                              _stream()), "dl_stem_wgrad_f32")
             return (None, dw, None) + extra
         gc = pool_bwd(g.contiguous(), a, win, ctx.act)
+        if not want_x and a.shape[3] % 64:
+            # a narrow network's conv1: the strided weight gradient of the narrow family, laid out as the parameter is
+            dw = narrow_wgrad(x8, gc, 3, stride=(1, 2)).permute(0, 3, 1, 2)
+            return (None, dw if tuple(dw.stride()) == tuple(w1.stride()) else dw.contiguous(), None) + extra
         xp = torch.cat((x8[:, :, -1:], x8, x8[:, :, :1]), dim=2).permute(0, 3, 1, 2)       # wrapped, channels_last strides
         gx, dw, _ = torch.ops.aten.convolution_backward(gc.permute(0, 3, 1, 2), xp, w1, None, (1, 2), (1, 0), (1, 1), False,
                                                         (0, 0), 1, (want_x, True, False))
@@ -609,6 +633,55 @@ def tower_supported(x_shape):
     elements (the C side's 32-bit offsets)."""
     B, C, H, W = x_shape
     return C == 8 and B >= 1 and H >= 1 and W >= 1 and B * H * W * TOWER_PITCH < (1 << 31)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Narrow pose networks (``factor_fewer_resnet_channels`` 2 and 4): the layers whose channel counts are not multiples of 64 on the narrow
+# family's strided / 1x1 / residual members (csrc/narrow.hip).
+def narrow_ok(cin, cout):
+    """The channel domain of the narrow family (csrc/narrow.hip: nr_channels_ok), restated."""
+    return 4 <= cin <= 64 and 8 <= cout <= 64 and cin % 4 == 0 and cout % 8 == 0
+
+
+def narrow_conv(x, w_krsc, stride=(1, 1), act=0, epilogue=0, add=None, dsrc=None, transposed=False):
+    """``conv_nhwc`` on the narrow family (``dl_narrow_conv2d_nhwc_f32``): same arguments, 4..64 channels, stride (1,1) or (1,2)."""
+    lib = _lib.load()
+    N, H, W, C = x.shape
+    ks = w_krsc.shape[1]
+    K = w_krsc.shape[3] if transposed else w_krsc.shape[0]
+    y = _empty((N, out_size(H, stride[0]), out_size(W, stride[1]), K), torch.float32, x.device)
+    _lib.check(lib.dl_narrow_conv2d_nhwc_f32(_ptr(x), _ptr(w_krsc), _ptr(y), _ptr(add), _ptr(dsrc), N, H, W, C, K, ks, stride[0], stride[1],
+                                             int(transposed), int(act), int(epilogue), _stream()), "dl_narrow_conv2d_nhwc_f32")
+    return y
+
+
+def narrow_dgrad_strided(g, w_krsc, stride, in_hw, act=0, epilogue=0, add_grid=None, dsrc=None, dense=False):
+    """``dgrad_strided`` on the narrow family (``dl_narrow_dgrad_strided_nhwc_f32``): the output gradient read with zeros between its
+    columns, as addressing."""
+    lib = _lib.load()
+    N, Ho, Wo, K = g.shape
+    H, W = int(in_hw[0]), int(in_hw[1])
+    assert Ho == out_size(H, stride[0]) and Wo == out_size(W, stride[1]), (g.shape, in_hw, stride)
+    ks, C = w_krsc.shape[1], w_krsc.shape[3]
+    dx = _empty((N, Ho, Wo, C) if dense else (N, H, W, C), torch.float32, g.device)
+    _lib.check(lib.dl_narrow_dgrad_strided_nhwc_f32(_ptr(g), _ptr(w_krsc), _ptr(dx), _ptr(add_grid), _ptr(dsrc), N, H, W, K, C, ks, stride[0],
+                                                    stride[1], int(dense), int(act), int(epilogue), _stream()), "dl_narrow_dgrad_strided_nhwc_f32")
+    return dx
+
+
+def narrow_wgrad(x, g, ks, stride=(1, 1)):
+    """``wgrad_nhwc`` on the narrow family (``dl_narrow_wgrad_nhwc_f32``): fixed-order partial sums, a launch pair per layer."""
+    lib = _lib.load()
+    N, H, W, C = x.shape
+    K = g.shape[3]
+    nbytes = lib.dl_narrow_wgrad_workspace_bytes(N, H, W, C, K, ks, stride[0], stride[1])
+    if not nbytes:
+        raise _lib.DeloraHipError(f"dl_narrow_wgrad_nhwc_f32 does not support x {tuple(x.shape)} -> K={K}, kernel {ks}, stride {tuple(stride)}")
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
+    dw = torch.empty((K, ks, ks, C), dtype=torch.float32, device=x.device)
+    _lib.check(lib.dl_narrow_wgrad_nhwc_f32(_ptr(x), _ptr(g), _ptr(dw), _ptr(ws), N, H, W, C, K, ks, stride[0], stride[1], _stream()),
+               "dl_narrow_wgrad_nhwc_f32")
+    return dw
 
 
 def _tower_backward(g, gv, acts, weights, act, N, H, W):
@@ -881,6 +954,25 @@ class _PairLayer(_Layer):
         return wino_strided_dgrad(g, self.bwd, self.cin, self.stride, in_hw, act=act, epilogue=epilogue, add_grid=add, dsrc=dsrc)
 
 
+class _NarrowLayer(_Layer):
+    """fp32 layers of a narrow network, fewer than 64 channels on one side (csrc/narrow.hip), on the raw weight: 3x3 and 1x1, stride
+    (1,1) and (1,2).  A stride-1 layer's input gradient is the transposed convolution (the grid of a stride-1 down-sampling block is the
+    image: its addend is a plain ADD); a strided one's reads the gradient with zeros between its columns (``narrow_dgrad_strided``)."""
+
+    def prepare(self, want_bwd):
+        self.u = weight_storage(self.w)
+
+    def fwd(self, x, act=0, epilogue=0, add=None):
+        return narrow_conv(x, self.u, stride=self.stride, act=act, epilogue=epilogue, add=add)
+
+    def dgrad(self, g, in_hw, act=0, epilogue=0, add=None, dsrc=None, dense=False):
+        if tuple(self.stride) != (1, 1):
+            return narrow_dgrad_strided(g, weight_storage(self.w), self.stride, in_hw, act=act, epilogue=epilogue, add_grid=add, dsrc=dsrc, dense=dense)
+        if epilogue & EPI_ADD_GRID:
+            epilogue = (epilogue & ~EPI_ADD_GRID) | EPI_ADD
+        return narrow_conv(g, weight_storage(self.w), act=act, epilogue=epilogue, add=add, dsrc=dsrc, transposed=True)
+
+
 class _HalfLayer(_Layer):
     """bf16 / fp16 kernels (csrc/convh.hip) on the prepared copies ``u`` = w_fwd, ``bwd`` = w_bwd (``weights_batch_h``, one launch per
     segment); the same split between stride-1 and down-sampling layers as ``_DirectLayer``."""
@@ -899,12 +991,14 @@ def _layer_plan(x_shape, blocks, dtype):
     in weight order (conv1, conv2[, downsample]) from the input shape, the blocks, the precision and the module's switches.  fp32:
     stride-1 3x3 layers run as Winograd when ``USE_WINOGRAD`` and ``wino_ok``; conv1 of a strided down-sampling block that
     ``wino_strided_ok`` (``dl_wino_strided_takes``) accepts runs on the pixel-pair view (``USE_WINOGRAD_STRIDED``); every other layer,
-    the 1x1 ones included, runs the direct kernel.  Half precision has one family."""
+    the 1x1 ones included, runs the direct kernel.  fp32 layers with fewer than 64 channels on a side (``cin % 64 or cout % 64``, a
+    narrow network's first layers) run on the narrow family, whatever the switches say.  Half precision has one family."""
     plan, (N, H, W) = [], x_shape[:3]
     half = dtype != torch.float32
     for (cin, cout, stride, has_ds) in blocks:
         k1 = k2 = kd = _HalfLayer if half else _DirectLayer
-        if USE_WINOGRAD and not half:
+        narrow1 = not half and bool(cin % 64 or cout % 64) and narrow_ok(cin, cout)
+        if USE_WINOGRAD and not half and not narrow1:
             if stride == (1, 1):
                 k1 = _WinoLayer if wino_ok(H, W, cin, cout) else k1
             elif USE_WINOGRAD_STRIDED and tuple(stride) != (1, 1) and has_ds and wino_strided_ok(N, H, W, cin, cout, stride):
@@ -912,6 +1006,10 @@ def _layer_plan(x_shape, blocks, dtype):
         H, W = out_size(H, stride[0]), out_size(W, stride[1])
         if USE_WINOGRAD and not half and wino_ok(H, W, cout, cout):
             k2 = _WinoLayer
+        if narrow1:
+            k1 = kd = _NarrowLayer
+        if not half and cout % 64 and narrow_ok(cout, cout):
+            k2 = _NarrowLayer
         plan += [(k1, cin, cout, 3, stride, has_ds), (k2, cout, cout, 3, (1, 1), False)]
         if has_ds:
             plan.append((kd, cin, cout, 1, stride, True))
@@ -1024,7 +1122,7 @@ class RingSegment(torch.autograd.Function):
     def backward(ctx, dy):
         acts, rest, dsrc0 = _saved(ctx)                 # rest: the raw weights, then u_bwd of the layers that have one
         u_bwd = iter(rest[len(ctx.plan):])
-        layers = [kind(*shape, w, None if kind is _DirectLayer else next(u_bwd)) for (kind, *shape), w in zip(ctx.plan, rest)]
+        layers = [kind(*shape, w, None if kind in (_DirectLayer, _NarrowLayer) else next(u_bwd)) for (kind, *shape), w in zip(ctx.plan, rest)]
         return _segment_backward(ctx, layers, acts, dsrc0, dy, rest[:len(layers)], wgrad_batch)
 
 

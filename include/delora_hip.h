@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), the narrow convolution family dl_tower_* (purely additive: the number stays), dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays), inference without Python: dl_pose_net_* / dl_odometry_* (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
+#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), the narrow convolution family dl_tower_* (purely additive: the number stays), its strided / 1x1 / residual members for narrow pose networks dl_narrow_* (purely additive: the number stays),dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays), inference without Python: dl_pose_net_* / dl_odometry_* (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
 
 typedef void* dl_stream;
 
@@ -439,6 +439,44 @@ int dl_tower_conv3x3_nhwc_f32(const float* x, const float* w, float* y, const fl
 size_t dl_tower_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t K);
 int dl_tower_wgrad3x3_nhwc_f32(const float* x, const float* g, float* dw, void* workspace, int32_t N, int32_t H, int32_t W,
                                int32_t C, int32_t K, const int32_t* x_view, const int32_t* g_view, dl_stream stream);
+
+/*
+ * The narrow family for NARROW POSE NETWORKS (csrc/narrow.hip; factor_fewer_resnet_channels 2 and 4 of the reference's
+ * config/hyperparameters.yaml: widths 32/64/128/256 and 16/32/64/128): the layers whose channel counts are not multiples of 64 -- the
+ * stem's conv1, layer1, and the first layers of layer2 (and of layer3 at factor 4).  Same arithmetic, channel domain (C % 4 == 0,
+ * K % 8 == 0, 4 <= C <= 64, 8 <= K <= 64 for the LAYER's input / output channels), ring addressing and free image size as above, on
+ * DENSE tensors, plus what a residual network needs: ksize 3 or 1 (1x1: unpadded), stride (1,1) or (1,2) (output width
+ * Wo = ceil(W / 2)), a residual-add epilogue and the strided layers' input gradient.  N * H * W * 64 < 2^31 (DL_ERR_UNSUPPORTED beyond).
+ *
+ *   dl_narrow_conv2d_nhwc_f32         y [N][H][Wo][K] = epilogue(conv(x [N][H][W][C], w)), arguments and epilogue (DL_CONV_ADD, DL_CONV_ACT,
+ *       DL_CONV_DACT, in this order; add, dsrc [N][H][Wo][K]) as dl_conv2d_nhwc_f32.  transposed == 1 (stride (1,1) only): w is the FORWARD
+ *       weight [C'][ksize][ksize][K'] of the layer whose input gradient is wanted, x its output gradient (C = K', K = C').  At stride
+ *       (1,2) a workgroup's tile is 4 rows x 32 output columns (half the stride-1 tile: the staged halo and the LDS budget stay the
+ *       same, two workgroups per CU).
+ *   dl_narrow_dgrad_strided_nhwc_f32  input gradient of a stride-(1,2) layer, arguments as dl_conv2d_dgrad_strided_nhwc_f32 without the
+ *       seam workspace: H, W = the layer's INPUT image, g [N][H][ceil(W/2)][K], w the forward weight [K][ksize][ksize][C], dx [N][H][W][C].
+ *       The gradient is read as if zeros stood between its columns (addressing only) and the stride-1 transposed convolution runs on
+ *       that ring: exact on any width, twice the MFMA work of a phase-split form.  epilogue: DL_CONV_ADD_GRID (v += add_grid
+ *       [n][h][w / 2][c] on the even columns), then DL_CONV_DACT (dsrc [N][H][W][C]).  dense != 0 (ksize 1, no epilogue): the 1x1
+ *       layer's gradient on the grid, [N][H][ceil(W/2)][C], meant as add_grid of the 3x3 layer's call.
+ *   dl_narrow_wgrad_nhwc_f32          dw [K][ksize][ksize][C] from x [N][H][W][C] and g [N][H][Wo][K]: partial sums per workgroup in
+ *       `workspace` (dl_narrow_wgrad_workspace_bytes(...) bytes; 0 for shapes the launch refuses; need not be initialised), summed in
+ *       a fixed order by a second launch.  No float atomics: bit-identical from run to run.
+ * Refusals -- a null x / w / y / g / dx / dw / workspace, an unknown epilogue flag, a bad act, a flag without its operand
+ * (DL_ERR_INVALID_ARGUMENT); channels outside the domain, another ksize or stride, transposed with a stride
+ * (DL_ERR_UNSUPPORTED) -- happen before any launch, through dl_last_error.  No synchronisation, no allocation; launches go to the
+ * caller's stream (capturable).
+ */
+int dl_narrow_conv2d_nhwc_f32(const float* x, const float* w, float* y, const float* add, const float* dsrc, int32_t N, int32_t H,
+                              int32_t W, int32_t C, int32_t K, int32_t ksize, int32_t stride_h, int32_t stride_w, int32_t transposed,
+                              int32_t act, uint32_t epilogue, dl_stream stream);
+int dl_narrow_dgrad_strided_nhwc_f32(const float* g, const float* w, float* dx, const float* add_grid, const float* dsrc, int32_t N,
+                                     int32_t H, int32_t W, int32_t K, int32_t C, int32_t ksize, int32_t stride_h, int32_t stride_w,
+                                     int32_t dense, int32_t act, uint32_t epilogue, dl_stream stream);
+size_t dl_narrow_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t K, int32_t ksize, int32_t stride_h,
+                                       int32_t stride_w);
+int dl_narrow_wgrad_nhwc_f32(const float* x, const float* g, float* dw, void* workspace, int32_t N, int32_t H, int32_t W, int32_t C,
+                             int32_t K, int32_t ksize, int32_t stride_h, int32_t stride_w, dl_stream stream);
 
 /*
  * The same stride-1 3x3 convolution (forward and, with the backward weight set, input gradient) as fused Winograd
