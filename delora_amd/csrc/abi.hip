@@ -56,18 +56,8 @@ int dl_fill_words(void* p, uint32_t value, size_t n_words, hipStream_t st) {
 #include <algorithm>
 #include <queue>
 namespace {
-double dl_batch_cost(const int* tiles, const int* chunks, int n, int machines, int partial_cost, long unit, int* nslabs) {
-  // units of layer i: tiles[i] * ns of size ceil(chunks / ns); dispatched by decreasing size to the first free machine
-  std::vector<std::pair<long, long>> runs;                    // (size, count)
-  double partials = 0;
-  for (int i = 0; i < n; ++i) {
-    long ns = (chunks[i] + unit - 1) / unit;
-    if (ns < 1) ns = 1;
-    nslabs[i] = (int)ns;
-    const long cps = (chunks[i] + ns - 1) / ns;
-    runs.push_back({cps, (long)tiles[i] * ns});
-    if (ns > 1) partials += (double)tiles[i] * ns;
-  }
+// Makespan of a launch: runs of (size, count) equal units, dispatched by decreasing size, each to the first free of `machines` slots
+long dl_makespan(std::vector<std::pair<long, long>> runs, int machines) {
   std::sort(runs.begin(), runs.end(), [](const std::pair<long, long>& a, const std::pair<long, long>& b) { return a.first > b.first; });
   std::priority_queue<long, std::vector<long>, std::greater<long>> free_at;
   for (int m = 0; m < machines; ++m) free_at.push(0);
@@ -79,7 +69,21 @@ double dl_batch_cost(const int* tiles, const int* chunks, int n, int machines, i
       free_at.push(t);
       makespan = std::max(makespan, t);
     }
-  return (double)makespan + (double)partial_cost * partials / machines;
+  return makespan;
+}
+double dl_batch_cost(const int* tiles, const int* chunks, int n, int machines, int partial_cost, long unit, int* nslabs) {
+  // units of layer i: tiles[i] * ns of size ceil(chunks / ns)
+  std::vector<std::pair<long, long>> runs;                    // (size, count)
+  double partials = 0;
+  for (int i = 0; i < n; ++i) {
+    long ns = (chunks[i] + unit - 1) / unit;
+    if (ns < 1) ns = 1;
+    nslabs[i] = (int)ns;
+    const long cps = (chunks[i] + ns - 1) / ns;
+    runs.push_back({cps, (long)tiles[i] * ns});
+    if (ns > 1) partials += (double)tiles[i] * ns;
+  }
+  return (double)dl_makespan(runs, machines) + (double)partial_cost * partials / machines;
 }
 std::mutex g_plan_mu;
 std::map<std::vector<int>, std::vector<int>> g_plan_cache;
@@ -128,20 +132,10 @@ extern "C" int64_t dl_wgrad_batch_plan(const int32_t* tiles, const int32_t* chun
   for (int i = 0; i < n; ++i)
     if (tiles[i] <= 0 || chunks[i] <= 0) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_wgrad_batch_plan: layer %d: tiles and chunks must be positive", i);
   dl_plan_batch(tiles, chunks, n, slots, partial_cost, nslabs);
-  // the makespan of the chosen plan (same simulation as the planner's, without the partial term)
+  // the makespan of the chosen plan (the planner's simulation, without the partial term)
   std::vector<std::pair<long, long>> runs;
   for (int i = 0; i < n; ++i) runs.push_back({((long)chunks[i] + nslabs[i] - 1) / nslabs[i], (long)tiles[i] * nslabs[i]});
-  std::sort(runs.begin(), runs.end(), [](const std::pair<long, long>& a, const std::pair<long, long>& b) { return a.first > b.first; });
-  std::priority_queue<long, std::vector<long>, std::greater<long>> free_at;
-  for (int m = 0; m < slots; ++m) free_at.push(0);
-  long makespan = 0;
-  for (const auto& r : runs)
-    for (long u = 0; u < r.second; ++u) {
-      const long t = free_at.top() + r.first;
-      free_at.pop(); free_at.push(t);
-      makespan = std::max(makespan, t);
-    }
-  return makespan;
+  return dl_makespan(runs, slots);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

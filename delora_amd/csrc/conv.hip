@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "conv_geom.h"
+#include "wgrad_batch.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -602,17 +603,12 @@ struct WgBatchArgs {
 };
 template <int BMK, int BNC, int PK, int SH, int SW, int KS, bool FAST = false>
 __global__ __launch_bounds__(CV_THREADS, 2) void k_wgrad_f32_batch(WgBatchArgs b) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < DL_WGRAD_BATCH; ++i)
-    if (i < b.n && (int)blockIdx.x >= b.first_wg[i]) l = i;
+  const int l = dl_table_slot<DL_WGRAD_BATCH>(b.first_wg, b.n, (int)blockIdx.x);
   const WgArgs a = b.layer[l];
   wgrad_f32_body<BMK, BNC, PK, SH, SW, KS, FAST>(a.x, a.g, a.part, a.N, a.H, a.W, a.C, a.K, a.Ho, a.Wo, a.chunks_per_slab, a.nslabs, (int)blockIdx.x - b.first_wg[l]);
 }
 
-// Sum of the slab partials in a fixed order (slab 0, 1, 2, ... per element: deterministic).  Eight slabs are loaded per
-// trip so that eight independent 16-byte loads are in flight per lane -- the one-load-per-trip form ran at 1.7 TB/s.
-__device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ part, int nslabs, size_t count, float* __restrict__ dw, size_t i);
+// Sum of the slab partials in a fixed order (dl_slab_sum_body, wgrad_batch.h)
 struct WgReduceBatchArgs {
   const float* part[DL_WGRAD_BATCH];
   float* dw[DL_WGRAD_BATCH];
@@ -622,29 +618,12 @@ struct WgReduceBatchArgs {
   int n;
 };
 __global__ __launch_bounds__(CV_THREADS) void k_wgrad_reduce_batch(WgReduceBatchArgs b) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < DL_WGRAD_BATCH; ++i)
-    if (i < b.n && (int)blockIdx.x >= b.first_block[i]) l = i;
-  wgrad_reduce_body(b.part[l], b.nslabs[l], b.count[l], b.dw[l], ((size_t)((int)blockIdx.x - b.first_block[l]) * CV_THREADS + threadIdx.x) * 4);
+  const int l = dl_table_slot<DL_WGRAD_BATCH>(b.first_block, b.n, (int)blockIdx.x);
+  dl_slab_sum_body(b.part[l], b.nslabs[l], b.count[l], b.dw[l], ((size_t)((int)blockIdx.x - b.first_block[l]) * CV_THREADS + threadIdx.x) * 4);
 }
 __global__ __launch_bounds__(CV_THREADS) void k_wgrad_reduce(const float* __restrict__ part, int nslabs, size_t count,
                                                              float* __restrict__ dw) {
-  wgrad_reduce_body(part, nslabs, count, dw, ((size_t)blockIdx.x * CV_THREADS + threadIdx.x) * 4);
-}
-__device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ part, int nslabs, size_t count, float* __restrict__ dw, size_t i) {
-  if (i >= count) return;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  int k = 0;
-  for (; k + 8 <= nslabs; k += 8) {
-    f32x4 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(part + (size_t)(k + u) * count + i));
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; k < nslabs; ++k) s += __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(part + (size_t)k * count + i));
-  *reinterpret_cast<f32x4*>(dw + i) = s;
+  dl_slab_sum_body(part, nslabs, count, dw, ((size_t)blockIdx.x * CV_THREADS + threadIdx.x) * 4);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -935,14 +914,8 @@ int g_wg_want = 512;
 static const int g_wg_want = 512;
 #endif
 
-static int wgrad_slabs(int total_chunks, int tiles) {
-  // enough workgroups to fill 256 CUs twice over (2 resident per CU); a slab is a run of pixel chunks
-  int want = (g_wg_want + tiles - 1) / tiles;
-  if (want > total_chunks) want = total_chunks;
-  if (want < 1) want = 1;
-  const int per = (total_chunks + want - 1) / want;
-  return (total_chunks + per - 1) / per;
-}
+// enough workgroups to fill 256 CUs twice over (2 resident per CU); a slab is a run of pixel chunks
+static int wgrad_slabs(int total_chunks, int tiles) { return dl_single_slabs(total_chunks, tiles, g_wg_want).nslabs; }
 
 extern "C" size_t dl_conv2d_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t K, int32_t ksize,
                                                   int32_t stride_h, int32_t stride_w) {
@@ -998,17 +971,14 @@ extern "C" int dl_conv2d_wgrad_nhwc_f32(const float* x, const float* g, float* d
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Weight gradients of several layers in one call (include/delora_hip.h: dl_wgrad_layer)
-#include <algorithm>
-#include <vector>
+// Weight gradients of several layers in one call (include/delora_hip.h: dl_wgrad_layer; the shared host side is wgrad_batch.h)
 namespace {
-struct WgItem {
+struct WgItem : DlBatchItem {
   WgArgs a;
-  float* dw;
-  size_t count;
-  int tiles, total_chunks, key, ks, sh, sw;
-  double flop, bytes;
+  int ks, sh, sw;
+  WgArgs args() const { WgArgs r = a; r.part = part; r.chunks_per_slab = p.chunks_per_slab; r.nslabs = p.nslabs; return r; }
 };
+const std::vector<int> kWgKeys{0, 1, 2, 3, 4, 5, 6, 7};
 int wg_batch_plan(const dl_wgrad_layer* L, int n, std::vector<WgItem>& items) {
   if (!L || n <= 0 || n > DL_WGRAD_BATCH) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_conv2d_wgrad_batch_nhwc_f32: 1..%d layers per call", DL_WGRAD_BATCH);
   items.resize(n);
@@ -1022,28 +992,17 @@ int wg_batch_plan(const dl_wgrad_layer* L, int n, std::vector<WgItem>& items) {
     WgItem& it = items[i];
     const int Ho = (l.H + l.stride_h - 1) / l.stride_h, Wo = (l.W + l.stride_w - 1) / l.stride_w;
     const int pk = wg_pk(l.stride_w, l.ksize);
+    const int chunks = l.N * Ho * ((Wo + pk - 1) / pk);
     it.a = WgArgs{(const float*)l.x, (const float*)l.g, nullptr, l.N, l.H, l.W, l.C, l.K, Ho, Wo, 0, 0};
-    it.dw = l.dw;
-    it.count = (size_t)l.K * l.ksize * l.ksize * l.C;
-    it.tiles = (l.K / 64) * (l.C / 64);
-    it.total_chunks = l.N * Ho * ((Wo + pk - 1) / pk);
+    it.sum = l.dw;                                        // a single slab is the gradient itself
+    it.plane = (size_t)l.K * l.ksize * l.ksize * l.C;
+    it.p = DlSlabPlan{(l.K / 64) * (l.C / 64), chunks, chunks, 0, 0};
     it.ks = l.ksize; it.sh = l.stride_h; it.sw = l.stride_w;
     it.key = (l.ksize == 3 ? 4 : 0) + (l.stride_h - 1) * 2 + (l.stride_w - 1);
     it.flop = 2.0 * l.N * Ho * Wo * (double)l.K * l.C * l.ksize * l.ksize;
-    it.bytes = 4.0 * ((double)l.N * l.H * l.W * l.C + (double)l.N * Ho * Wo * l.K + (double)it.count);
+    it.bytes = 4.0 * ((double)l.N * l.H * l.W * l.C + (double)l.N * Ho * Wo * l.K + (double)it.plane);
   }
-  for (int key = 0; key < 8; ++key) {
-    std::vector<int> tl, ch, idx;
-    for (int i = 0; i < n; ++i) if (items[i].key == key) { tl.push_back(items[i].tiles); ch.push_back(items[i].total_chunks); idx.push_back(i); }
-    if (idx.empty()) continue;
-    std::vector<int> ns(idx.size());
-    dl_plan_batch(tl.data(), ch.data(), (int)idx.size(), g_wg_want, 20, ns.data());   // two 256-thread workgroups per CU
-    for (size_t j = 0; j < idx.size(); ++j) {
-      WgItem& it = items[idx[j]];
-      it.a.chunks_per_slab = (it.total_chunks + ns[j] - 1) / ns[j];
-      it.a.nslabs = (it.total_chunks + it.a.chunks_per_slab - 1) / it.a.chunks_per_slab;
-    }
-  }
+  dl_plan_slabs(items, kWgKeys, g_wg_want, 20);           // two 256-thread workgroups per CU
   return DL_OK;
 }
 template <int SH, int SW, int KS>
@@ -1063,9 +1022,7 @@ void launch_wgrad_batch(const WgBatchArgs& b, int wgs, const DlProfTag& tag, hip
 extern "C" size_t dl_conv2d_wgrad_batch_workspace_bytes(const dl_wgrad_layer* layers, int32_t n) {
   std::vector<WgItem> items;
   if (wg_batch_plan(layers, n, items)) return 0;
-  size_t floats = 4;
-  for (const auto& it : items) if (it.a.nslabs > 1) floats += (size_t)it.a.nslabs * it.count;
-  return floats * sizeof(float);
+  return dl_carve_workspace(items, nullptr, false, 4) * sizeof(float);      // (never zero: 0 means "not supported")
 }
 
 extern "C" int dl_conv2d_wgrad_batch_nhwc_f32(const dl_wgrad_layer* layers, int32_t n, void* workspace, dl_stream stream) {
@@ -1076,44 +1033,25 @@ extern "C" int dl_conv2d_wgrad_batch_nhwc_f32(const dl_wgrad_layer* layers, int3
   for (int i = 0; i < n; ++i)
     if (!layers[i].x || !layers[i].g || !layers[i].dw) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_conv2d_wgrad_batch_nhwc_f32: layer %d: null pointer", i);
   hipStream_t st = (hipStream_t)stream;
-  float* wsf = (float*)workspace;
-  for (auto& it : items) {
-    if (it.a.nslabs > 1) { it.a.part = wsf; wsf += (size_t)it.a.nslabs * it.count; }
-    else it.a.part = it.dw;                               // a single slab is the gradient itself
-  }
-  for (int key = 0; key < 8; ++key) {
-    std::vector<const WgItem*> grp;
-    for (const auto& it : items) if (it.key == key) grp.push_back(&it);
-    if (grp.empty()) continue;
-    std::stable_sort(grp.begin(), grp.end(), [](const WgItem* x, const WgItem* y) { return x->a.chunks_per_slab > y->a.chunks_per_slab; });
+  dl_carve_workspace(items, (float*)workspace, false, 4);
+  std::vector<const WgItem*> grp;
+  for (int key : kWgKeys) {
     WgBatchArgs b{};
-    b.n = (int)grp.size();
-    int wgs = 0;
-    double flop = 0, bytes = 0;
-    for (int i = 0; i < b.n; ++i) {
-      b.layer[i] = grp[i]->a;
-      b.first_wg[i] = wgs;
-      wgs += grp[i]->tiles * grp[i]->a.nslabs;
-      flop += grp[i]->flop; bytes += grp[i]->bytes;
-    }
-    b.first_wg[b.n] = wgs;
+    const DlGroupWork w = dl_fill_group(items, key, [](const WgItem& it) { return it.p.chunks_per_slab; }, b, grp);
+    if (!b.n) continue;
     const WgItem& f = *grp[0];
-    const DlProfTag tag{"k_wgrad_f32", b.n > 1 ? "wgrad-batch" : "wgrad", f.a.N, f.a.H, f.a.W, f.a.C, f.a.K, f.ks, f.sh, f.sw, flop, bytes};
-    if (f.ks == 3 && f.sh == 1 && f.sw == 1) launch_wgrad_batch<1, 1, 3>(b, wgs, tag, st);
-    else if (f.ks == 3 && f.sh == 1 && f.sw == 2) launch_wgrad_batch<1, 2, 3>(b, wgs, tag, st);
-    else if (f.ks == 3 && f.sh == 2 && f.sw == 2) launch_wgrad_batch<2, 2, 3>(b, wgs, tag, st);
-    else if (f.ks == 1 && f.sh == 1 && f.sw == 2) launch_wgrad_batch<1, 2, 1>(b, wgs, tag, st);
-    else launch_wgrad_batch<2, 2, 1>(b, wgs, tag, st);
+    const DlProfTag tag{"k_wgrad_f32", b.n > 1 ? "wgrad-batch" : "wgrad", f.a.N, f.a.H, f.a.W, f.a.C, f.a.K, f.ks, f.sh, f.sw, w.flop, w.bytes};
+    if (f.ks == 3 && f.sh == 1 && f.sw == 1) launch_wgrad_batch<1, 1, 3>(b, w.wgs, tag, st);
+    else if (f.ks == 3 && f.sh == 1 && f.sw == 2) launch_wgrad_batch<1, 2, 3>(b, w.wgs, tag, st);
+    else if (f.ks == 3 && f.sh == 2 && f.sw == 2) launch_wgrad_batch<2, 2, 3>(b, w.wgs, tag, st);
+    else if (f.ks == 1 && f.sh == 1 && f.sw == 2) launch_wgrad_batch<1, 2, 1>(b, w.wgs, tag, st);
+    else launch_wgrad_batch<2, 2, 1>(b, w.wgs, tag, st);
   }
   WgReduceBatchArgs r{};
-  int blocks = 0;
-  for (const auto& it : items) if (it.a.nslabs > 1) {
-    r.part[r.n] = it.a.part; r.dw[r.n] = it.dw; r.count[r.n] = (unsigned)it.count; r.nslabs[r.n] = it.a.nslabs;
-    r.first_block[r.n] = blocks;
-    blocks += (int)((it.count / 4 + CV_THREADS - 1) / CV_THREADS);
-    ++r.n;
-  }
-  r.first_block[r.n] = blocks;
+  const int blocks = dl_fill_post(items, true, CV_THREADS, r, [](WgReduceBatchArgs& t, int j, const WgItem& it) {
+    t.part[j] = it.part; t.dw[j] = it.sum; t.count[j] = (unsigned)it.plane; t.nslabs[j] = it.p.nslabs;
+    return it.plane / 4;
+  });
   if (r.n) DL_LAUNCH_PLAIN(k_wgrad_reduce_batch, dim3(blocks), dim3(CV_THREADS), st, r);
   return dl_check_launch("dl_conv2d_wgrad_batch_nhwc_f32");
 }

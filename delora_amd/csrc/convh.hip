@@ -30,6 +30,7 @@
 #include "common.h"
 #include "conv_geom.h"
 #include "convh_common.h"
+#include "wgrad_batch.h"
 
 // number of i in [0, n) with i % parts == part (DMA pieces a wave issues in one part of a chunk's input tile)
 constexpr int ch_count_parts(int n, int part, int parts) { int c = 0; for (int i = 0; i < n; ++i) c += (i % parts == part) ? 1 : 0; return c; }
@@ -390,10 +391,7 @@ struct WprepBatchArgs {
 template <bool F16>
 __global__ __launch_bounds__(256) void k_wprep_batch_h(WprepBatchArgs a) {
   __shared__ float tile[32][33];
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < DL_CONVH_BATCH; ++i)
-    if (i < a.n && (int)blockIdx.x >= a.first_block[i]) l = i;
+  const int l = dl_table_slot<DL_CONVH_BATCH>(a.first_block, a.n, (int)blockIdx.x);
   const int K = a.K[l], T = a.T[l], C = a.C[l];
   const float* __restrict__ w = a.w[l];
   u16* __restrict__ w_fwd = a.w_fwd[l];

@@ -15,6 +15,7 @@
 // chunks (PR output rows x PK columns each, double-buffered, one barrier per chunk); fp32 slab partials are summed in a fixed
 // order by k_wgradh_reduce (deterministic, no float atomics).  Rows outside the image are read from a page of zeros.
 #include "convh_common.h"
+#include "wgrad_batch.h"
 
 
 struct WgradHArgs {
@@ -262,29 +263,12 @@ struct WgradHBatchArgs {
 };
 template <bool F16, int BMK, int PK, int PR, int SH, int SW, int KS>
 __global__ __launch_bounds__(64 * (BMK / 32) * 2, 2) void k_wgradh_batch(WgradHBatchArgs b) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < DL_WGRAD_BATCH; ++i)
-    if (i < b.n && (int)blockIdx.x >= b.first_wg[i]) l = i;
+  const int l = dl_table_slot<DL_WGRAD_BATCH>(b.first_wg, b.n, (int)blockIdx.x);
   const WgradHArgs a = b.layer[l];
   wgradh_body<F16, BMK, PK, PR, SH, SW, KS>(a, (int)blockIdx.x - b.first_wg[l]);
 }
 
-// dw = sum of the slab partials in a fixed order (slab 0, 1, 2, ...), eight 16-byte loads in flight per lane
-__device__ __forceinline__ void wgradh_reduce_body(const float* __restrict__ part, int nslabs, size_t count, float* __restrict__ dw, size_t i) {
-  if (i >= count) return;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  int k = 0;
-  for (; k + 8 <= nslabs; k += 8) {
-    f32x4 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(part + (size_t)(k + u) * count + i));
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; k < nslabs; ++k) s += __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(part + (size_t)k * count + i));
-  *reinterpret_cast<f32x4*>(dw + i) = s;
-}
+// dw = sum of the slab partials in a fixed order (dl_slab_sum_body, wgrad_batch.h)
 struct WgradHReduceBatchArgs {
   const float* part[DL_WGRAD_BATCH];
   float* dw[DL_WGRAD_BATCH];
@@ -294,14 +278,11 @@ struct WgradHReduceBatchArgs {
   int n;
 };
 __global__ __launch_bounds__(256) void k_wgradh_reduce_batch(WgradHReduceBatchArgs b) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < DL_WGRAD_BATCH; ++i)
-    if (i < b.n && (int)blockIdx.x >= b.first_block[i]) l = i;
-  wgradh_reduce_body(b.part[l], b.nslabs[l], b.count[l], b.dw[l], ((size_t)((int)blockIdx.x - b.first_block[l]) * 256 + threadIdx.x) * 4);
+  const int l = dl_table_slot<DL_WGRAD_BATCH>(b.first_block, b.n, (int)blockIdx.x);
+  dl_slab_sum_body(b.part[l], b.nslabs[l], b.count[l], b.dw[l], ((size_t)((int)blockIdx.x - b.first_block[l]) * 256 + threadIdx.x) * 4);
 }
 __global__ __launch_bounds__(256) void k_wgradh_reduce(const float* __restrict__ part, int nslabs, size_t count, float* __restrict__ dw) {
-  wgradh_reduce_body(part, nslabs, count, dw, ((size_t)blockIdx.x * 256 + threadIdx.x) * 4);
+  dl_slab_sum_body(part, nslabs, count, dw, ((size_t)blockIdx.x * 256 + threadIdx.x) * 4);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -311,8 +292,8 @@ int g_wh_want = 256;
 static const int g_wh_want = 256;
 #endif
 
-struct WgradHPlan {
-  int bmk, pk, pr, tiles, total_chunks, nslabs, chunks_per_slab;
+struct WgradHPlan : DlSlabPlan {
+  int bmk, pk, pr;
 };
 
 // chunk = PR = 2 output rows x PK columns; PK = 64 for stride-1 layers (32 when the row is narrower), 32 for strided ones
@@ -326,13 +307,8 @@ static bool wgradh_plan(int N, int H, int W, int C, int K, int ks, int sh, int s
   // 64-channel tiles run 4 waves per workgroup: the short chunk keeps two workgroups resident per CU.  Rows that do not divide into
   // chunks end in an overhanging chunk: 64-pixel chunks only where they waste no more of the row than 32-pixel ones
   p->pk = (sh == 1 && sw == 1 && p->bmk == 128 && (Wo + 63) / 64 * 64 == (Wo + 31) / 32 * 32) ? 64 : 32;
-  p->tiles = (K / p->bmk) * (C / 64);
-  p->total_chunks = N * ((Ho + p->pr - 1) / p->pr) * ((Wo + p->pk - 1) / p->pk);
-  int want = (g_wh_want + p->tiles - 1) / p->tiles;
-  if (want > p->total_chunks) want = p->total_chunks;
-  if (want < 1) want = 1;
-  p->chunks_per_slab = (p->total_chunks + want - 1) / want;
-  p->nslabs = (p->total_chunks + p->chunks_per_slab - 1) / p->chunks_per_slab;
+  const int tiles = (K / p->bmk) * (C / 64);
+  static_cast<DlSlabPlan&>(*p) = dl_single_slabs(N * ((Ho + p->pr - 1) / p->pr) * ((Wo + p->pk - 1) / p->pk), tiles, g_wh_want);
   return true;
 }
 
@@ -398,18 +374,12 @@ extern "C" int dl_conv2d_wgrad_nhwc_h(const void* x, const void* g, float* dw, v
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Several layers in one call (see k_wgradh_batch).  Layers that share a kernel instantiation form a group = one launch; the slab
-// count of every layer follows from the group's total work: a workgroup should reduce about total / (one workgroup per CU) chunks.
-#include <algorithm>
-#include <vector>
-
+// count of every layer follows from the group's total work (wgrad_batch.h: the host side shared with the fp32 families).
 namespace {
-struct WgradHItem {
+struct WgradHItem : DlBatchItem {
   WgradHArgs a;
-  WgradHPlan p;
-  float* dw;
-  size_t count;            // elements of dw
-  int key, ks, sh, sw;     // kernel instantiation
-  double flop, bytes;
+  int bmk, pk, ks, sh, sw;     // kernel instantiation
+  WgradHArgs args() const { WgradHArgs r = a; r.part = part; r.chunks_per_slab = p.chunks_per_slab; r.nslabs = p.nslabs; return r; }
 };
 
 int wgradh_key(const WgradHPlan& p, int ks, int sh, int sw) { return (((p.bmk == 128 ? 1 : 0) * 2 + (p.pk == 64 ? 1 : 0)) * 4 + (sh - 1) * 2 + (sw - 1)) * 2 + (ks == 3 ? 1 : 0); }
@@ -421,35 +391,24 @@ int wgradh_batch_plan(const dl_wgrad_h_layer* L, int n, std::vector<WgradHItem>&
   for (int i = 0; i < n; ++i) {
     const dl_wgrad_h_layer& l = L[i];
     WgradHItem& it = items[i];
-    if (!wgradh_plan(l.N, l.H, l.W, l.C, l.K, l.ksize, l.stride_h, l.stride_w, &it.p))
+    WgradHPlan plan;
+    if (!wgradh_plan(l.N, l.H, l.W, l.C, l.K, l.ksize, l.stride_h, l.stride_w, &plan))
       return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_wgrad_batch_nhwc_h: layer %d: N=%d H=%d W=%d C=%d K=%d kernel %d stride (%d,%d) is not supported (C, K %% 64)",
                      i, l.N, l.H, l.W, l.C, l.K, l.ksize, l.stride_h, l.stride_w);
     const int Ho = (l.H + l.stride_h - 1) / l.stride_h, Wo = (l.W + l.stride_w - 1) / l.stride_w;
     if ((size_t)l.N * l.H * l.W * l.C >= ((size_t)1 << 30) || (size_t)l.N * Ho * Wo * l.K >= ((size_t)1 << 30))
       return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_wgrad_batch_nhwc_h: layer %d: tensors beyond 2^30 elements are not supported", i);
     it.a = WgradHArgs{(const u16*)l.x, (const u16*)l.g, nullptr, l.N, l.H, l.W, l.C, l.K, Ho, Wo, 0, 0};
-    it.dw = l.dw;
-    it.count = (size_t)l.K * l.ksize * l.ksize * l.C;
+    it.sum = l.dw;                                        // a layer with one slab writes its gradient directly
+    it.plane = (size_t)l.K * l.ksize * l.ksize * l.C;     // elements of dw
+    it.p = plan;                                          // (tiles and chunks; the slab counts are the table's, below)
+    it.bmk = plan.bmk; it.pk = plan.pk;
     it.ks = l.ksize; it.sh = l.stride_h; it.sw = l.stride_w;
-    it.key = wgradh_key(it.p, l.ksize, l.stride_h, l.stride_w);
+    it.key = wgradh_key(plan, l.ksize, l.stride_h, l.stride_w);
     it.flop = 2.0 * l.N * Ho * Wo * (double)l.K * l.C * l.ksize * l.ksize;
-    it.bytes = 2.0 * ((double)l.N * l.H * l.W * l.C + (double)l.N * Ho * Wo * l.K) + 4.0 * it.count;
+    it.bytes = 2.0 * ((double)l.N * l.H * l.W * l.C + (double)l.N * Ho * Wo * l.K) + 4.0 * it.plane;
   }
-  // slab counts per group
-  std::vector<int> keys;
-  for (const auto& it : items) if (std::find(keys.begin(), keys.end(), it.key) == keys.end()) keys.push_back(it.key);
-  for (int key : keys) {
-    std::vector<int> tl, ch, idx;
-    for (int i = 0; i < n; ++i) if (items[i].key == key) { tl.push_back(items[i].p.tiles); ch.push_back(items[i].p.total_chunks); idx.push_back(i); }
-    std::vector<int> ns(idx.size());
-    dl_plan_batch(tl.data(), ch.data(), (int)idx.size(), g_wh_want, 10, ns.data());
-    for (size_t j = 0; j < idx.size(); ++j) {
-      WgradHItem& it = items[idx[j]];
-      it.p.chunks_per_slab = (it.p.total_chunks + ns[j] - 1) / ns[j];
-      it.p.nslabs = (it.p.total_chunks + it.p.chunks_per_slab - 1) / it.p.chunks_per_slab;
-      it.a.chunks_per_slab = it.p.chunks_per_slab; it.a.nslabs = it.p.nslabs;
-    }
-  }
+  dl_plan_slabs(items, dl_keys_as_they_appear(items), g_wh_want, 10);
   return DL_OK;
 }
 
@@ -483,9 +442,7 @@ int wgradh_batch_dispatch(const WgradHBatchArgs& b, int wgs, int bmk, int pk, in
 extern "C" size_t dl_conv2d_wgrad_batch_h_workspace_bytes(const dl_wgrad_h_layer* layers, int32_t n) {
   std::vector<WgradHItem> items;
   if (wgradh_batch_plan(layers, n, items)) return 0;
-  size_t floats = 4;                                  // (never zero: 0 means "not supported")
-  for (const auto& it : items) if (it.p.nslabs > 1) floats += (size_t)it.p.nslabs * it.count;
-  return floats * sizeof(float);
+  return dl_carve_workspace(items, nullptr, false, 4) * sizeof(float);      // (never zero: 0 means "not supported")
 }
 
 extern "C" int dl_conv2d_wgrad_batch_nhwc_h(const dl_wgrad_h_layer* layers, int32_t n, void* workspace, int32_t dtype, dl_stream stream) {
@@ -497,46 +454,24 @@ extern "C" int dl_conv2d_wgrad_batch_nhwc_h(const dl_wgrad_h_layer* layers, int3
   for (int i = 0; i < n; ++i)
     if (!layers[i].x || !layers[i].g || !layers[i].dw) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_conv2d_wgrad_batch_nhwc_h: layer %d: null pointer", i);
   hipStream_t st = (hipStream_t)stream;
-  // partial buffers: a layer with one slab writes its gradient directly
-  float* wsf = (float*)workspace;
-  for (auto& it : items) {
-    if (it.p.nslabs > 1) { it.a.part = wsf; wsf += (size_t)it.p.nslabs * it.count; }
-    else it.a.part = it.dw;
-  }
-  std::vector<int> keys;
-  for (const auto& it : items) if (std::find(keys.begin(), keys.end(), it.key) == keys.end()) keys.push_back(it.key);
-  for (int key : keys) {
-    std::vector<const WgradHItem*> grp;
-    for (const auto& it : items) if (it.key == key) grp.push_back(&it);
-    std::stable_sort(grp.begin(), grp.end(), [](const WgradHItem* x, const WgradHItem* y) { return x->p.chunks_per_slab > y->p.chunks_per_slab; });
+  dl_carve_workspace(items, (float*)workspace, false, 4);
+  std::vector<const WgradHItem*> grp;
+  for (int key : dl_keys_as_they_appear(items)) {
     WgradHBatchArgs b{};
-    b.n = (int)grp.size();
-    int wgs = 0;
-    double flop = 0, bytes = 0;
-    for (int i = 0; i < b.n; ++i) {
-      b.layer[i] = grp[i]->a;
-      b.first_wg[i] = wgs;
-      wgs += grp[i]->p.tiles * grp[i]->p.nslabs;
-      flop += grp[i]->flop; bytes += grp[i]->bytes;
-    }
-    b.first_wg[b.n] = wgs;
+    const DlGroupWork w = dl_fill_group(items, key, [](const WgradHItem& it) { return it.p.chunks_per_slab; }, b, grp);
     const WgradHItem& f = *grp[0];
     // (profile row: the first layer's shape, the group's summed work)
-    const DlProfTag tag{"k_wgradh", b.n > 1 ? "wgrad-batch" : "wgrad", f.a.N, f.a.H, f.a.W, f.a.C, f.a.K, f.ks, f.sh, f.sw, flop, bytes};
-    const int rc = dtype == DL_DTYPE_F16 ? wgradh_batch_dispatch<true>(b, wgs, f.p.bmk, f.p.pk, f.ks, f.sh, f.sw, tag, st)
-                                         : wgradh_batch_dispatch<false>(b, wgs, f.p.bmk, f.p.pk, f.ks, f.sh, f.sw, tag, st);
+    const DlProfTag tag{"k_wgradh", b.n > 1 ? "wgrad-batch" : "wgrad", f.a.N, f.a.H, f.a.W, f.a.C, f.a.K, f.ks, f.sh, f.sw, w.flop, w.bytes};
+    const int rc = dtype == DL_DTYPE_F16 ? wgradh_batch_dispatch<true>(b, w.wgs, f.bmk, f.pk, f.ks, f.sh, f.sw, tag, st)
+                                         : wgradh_batch_dispatch<false>(b, w.wgs, f.bmk, f.pk, f.ks, f.sh, f.sw, tag, st);
     if (rc) return dl_fail(DL_ERR_UNSUPPORTED, "dl_conv2d_wgrad_batch_nhwc_h: no kernel for a layer group");
   }
   // one reduction launch for every layer that was split
   WgradHReduceBatchArgs r{};
-  int blocks = 0;
-  for (const auto& it : items) if (it.p.nslabs > 1) {
-    r.part[r.n] = it.a.part; r.dw[r.n] = it.dw; r.count[r.n] = (unsigned)it.count; r.nslabs[r.n] = it.p.nslabs;
-    r.first_block[r.n] = blocks;
-    blocks += (int)((it.count / 4 + 255) / 256);
-    ++r.n;
-  }
-  r.first_block[r.n] = blocks;
+  const int blocks = dl_fill_post(items, true, 256, r, [](WgradHReduceBatchArgs& t, int j, const WgradHItem& it) {
+    t.part[j] = it.part; t.dw[j] = it.sum; t.count[j] = (unsigned)it.plane; t.nslabs[j] = it.p.nslabs;
+    return it.plane / 4;
+  });
   if (r.n) DL_LAUNCH_PLAIN(k_wgradh_reduce_batch, dim3(blocks), dim3(256), st, r);
   return dl_check_launch("dl_conv2d_wgrad_batch_nhwc_h");
 }

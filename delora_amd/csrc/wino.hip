@@ -23,6 +23,7 @@
 // Numerics: fp32 throughout; Winograd F(2x2,3x3) adds/subtracts before and after the products, error ~1e-6 relative to the
 // layer's output scale (tests/test_gpu_conv.py bounds it against torch's direct convolution at 1e-4).
 #include "common.h"
+#include "wgrad_batch.h"
 #include <cstdlib>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -276,10 +277,7 @@ struct WinoBatchArgs {
 // reference's default batch-1 step.)
 __global__ __launch_bounds__(256) void k_wino_weights_batch(WinoBatchArgs a) {
   __shared__ float stage[16 * 256];
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < DL_WINO_BATCH; ++i)
-    if (i < a.n && (int)blockIdx.x >= a.first_block[i]) l = i;
+  const int l = dl_table_slot<DL_WINO_BATCH>(a.first_block, a.n, (int)blockIdx.x);
   const int K = a.K[l], C = a.C[l];
   const int blk = (int)blockIdx.x - a.first_block[l];
   const int cblocks = C / 32;
@@ -1115,10 +1113,7 @@ struct WWBatchArgs {
 };
 template <bool RAG>
 __global__ __launch_bounds__(WW_THREADS) void k_wino_wgrad_batch(WWBatchArgs b) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < DL_WGRAD_BATCH; ++i)
-    if (i < b.n && (int)blockIdx.x >= b.first_wg[i]) l = i;
+  const int l = dl_table_slot<DL_WGRAD_BATCH>(b.first_wg, b.n, (int)blockIdx.x);
   const WWArgs a = b.layer[l];
 #ifndef WW_OLD
   if constexpr (!RAG) wino_wgrad_body3(a, (int)blockIdx.x - b.first_wg[l]);
@@ -1133,7 +1128,7 @@ __global__ __launch_bounds__(WW_THREADS) void k_wino_wgrad_batch(WWBatchArgs b) 
 // with both bodies: each stays below the stride-1 body's registers, and a second launch would leave the chip idle at the tail of the first.
 #define SW_ITEMS (2 * DL_WGRAD_BATCH)
 struct SWBatchArgs {
-  WWArgs item[SW_ITEMS];                 // the pair view: W = W/2 pixels of C = 2C channels; ws = the item's own partials
+  WWArgs layer[SW_ITEMS];                // an item each; the pair view: W = W/2 pixels of C = 2C channels; ws = the item's own partials
   int first_wg[SW_ITEMS + 1];
   int odd[SW_ITEMS];
   int n;
@@ -1141,11 +1136,8 @@ struct SWBatchArgs {
 // ALL12 (DL_SWGRAD_ALL12=1, a measurement switch of tools/conv_harness): the even-pixel blocks run the 12-plane body as well
 template <bool ALL12>
 __global__ __launch_bounds__(WW_THREADS) void k_wino_wgrad_strided_batch(SWBatchArgs b) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < SW_ITEMS; ++i)
-    if (i < b.n && (int)blockIdx.x >= b.first_wg[i]) l = i;
-  const WWArgs a = b.item[l];
+  const int l = dl_table_slot<SW_ITEMS>(b.first_wg, b.n, (int)blockIdx.x);
+  const WWArgs a = b.layer[l];
   if (b.odd[l]) wino_wgrad_body3_live<0x7>(a, (int)blockIdx.x - b.first_wg[l]);
   else if constexpr (ALL12) wino_wgrad_body3_live<0x7, false>(a, (int)blockIdx.x - b.first_wg[l]);
   else wino_wgrad_body3_live<0x6>(a, (int)blockIdx.x - b.first_wg[l]);
@@ -1176,17 +1168,11 @@ struct WWPostArgs {
   int n;
 };
 __global__ __launch_bounds__(256) void k_wino_wgrad_sum_batch(WWPostArgs b) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < DL_WGRAD_BATCH; ++i)
-    if (i < b.n && (int)blockIdx.x >= b.first_block[i]) l = i;
+  const int l = dl_table_slot<DL_WGRAD_BATCH>(b.first_block, b.n, (int)blockIdx.x);
   wino_wgrad_sum_body(b.src[l], b.nslabs[l], (size_t)16 * b.K[l] * b.C[l] / 4, b.dst[l], (size_t)((int)blockIdx.x - b.first_block[l]) * 256 + threadIdx.x);
 }
 __global__ __launch_bounds__(256) void k_wino_wgrad_out_batch(WWPostArgs b) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < DL_WGRAD_BATCH; ++i)
-    if (i < b.n && (int)blockIdx.x >= b.first_block[i]) l = i;
+  const int l = dl_table_slot<DL_WGRAD_BATCH>(b.first_block, b.n, (int)blockIdx.x);
   wino_wgrad_out_body(b.src[l], b.K[l], b.C[l], b.dst[l], (size_t)((int)blockIdx.x - b.first_block[l]) * 256 + threadIdx.x);
 }
 
@@ -1228,13 +1214,7 @@ static int wn_cu_count() {
   return cus;
 }
 
-static int ww_slabs(int total_chunks, int tiles) {
-  int want = (256 + tiles - 1) / tiles;              // one 512-thread workgroup per CU
-  if (want > total_chunks) want = total_chunks;
-  if (want < 1) want = 1;
-  const int per = (total_chunks + want - 1) / want;
-  return (total_chunks + per - 1) / per;
-}
+static int ww_slabs(int total_chunks, int tiles) { return dl_single_slabs(total_chunks, tiles, 256).nslabs; }      // one 512-thread workgroup per CU
 
 static bool ww_supported(int N, int H, int W, int C, int K) {
   return N > 0 && H > 0 && W >= 2 && C % 64 == 0 && K % 64 == 0 && (size_t)N * H * W * (C > K ? C : K) < ((size_t)1 << 31) &&
@@ -1274,17 +1254,14 @@ extern "C" int dl_wino_wgrad3x3_nhwc_f32(const float* x, const float* g, float* 
   return dl_check_launch("dl_wino_wgrad3x3_nhwc_f32");
 }
 
-// ---- several layers in one call
-#include <algorithm>
-#include <vector>
+// ---- several layers in one call (the host side shared with the other families: wgrad_batch.h)
 namespace {
-struct WWItem {
+struct WWItem : DlBatchItem {          // key: 1 for an image that does not divide into chunks of 8 tiles (RAG)
   WWArgs a;
   float* dw;
-  float* usum;
-  int tiles, total_chunks, rag;
-  double flop, bytes;
+  WWArgs args() const { WWArgs r = a; r.ws = part; r.chunks_per_slab = p.chunks_per_slab; r.nslabs = p.nslabs; return r; }
 };
+const std::vector<int> kWWKeys{0, 1};
 int ww_batch_plan(const dl_wgrad_layer* L, int n, std::vector<WWItem>& items) {
   if (!L || n <= 0 || n > DL_WGRAD_BATCH) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_wino_wgrad3x3_batch_nhwc_f32: 1..%d layers per call", DL_WGRAD_BATCH);
   items.resize(n);
@@ -1296,24 +1273,13 @@ int ww_batch_plan(const dl_wgrad_layer* L, int n, std::vector<WWItem>& items) {
     WWItem& it = items[i];
     it.a = WWArgs{(const float*)l.x, (const float*)l.g, nullptr, l.N, l.H, l.W, l.C, l.K, 0, 0};
     it.dw = l.dw;
-    it.tiles = (l.K / 64) * (l.C / 64);
-    it.total_chunks = ww_chunks(l.N, l.H, l.W);
-    it.rag = ww_exact(l.H, l.W) ? 0 : 1;
+    it.plane = (size_t)16 * l.K * l.C;
+    it.p = DlSlabPlan{(l.K / 64) * (l.C / 64), ww_chunks(l.N, l.H, l.W), ww_chunks(l.N, l.H, l.W), 0, 0};
+    it.key = ww_exact(l.H, l.W) ? 0 : 1;
     it.flop = 2.0 * 16.0 * (double)l.N * ((l.H + 1) / 2) * ((l.W + 1) / 2) * (double)l.C * l.K;
     it.bytes = 4.0 * ((double)l.N * l.H * l.W * (l.C + l.K) + 9.0 * l.C * l.K);
   }
-  for (int rag = 0; rag < 2; ++rag) {
-    std::vector<int> tl, ch, idx;
-    for (int i = 0; i < n; ++i) if (items[i].rag == rag) { tl.push_back(items[i].tiles); ch.push_back(items[i].total_chunks); idx.push_back(i); }
-    if (idx.empty()) continue;
-    std::vector<int> ns(idx.size());
-    dl_plan_batch(tl.data(), ch.data(), (int)idx.size(), 256, 10, ns.data());         // one 512-thread workgroup per CU
-    for (size_t j = 0; j < idx.size(); ++j) {
-      WWItem& it = items[idx[j]];
-      it.a.chunks_per_slab = (it.total_chunks + ns[j] - 1) / ns[j];
-      it.a.nslabs = (it.total_chunks + it.a.chunks_per_slab - 1) / it.a.chunks_per_slab;
-    }
-  }
+  dl_plan_slabs(items, kWWKeys, 256, 10);                 // one 512-thread workgroup per CU
   return DL_OK;
 }
 }  // namespace
@@ -1322,9 +1288,7 @@ int ww_batch_plan(const dl_wgrad_layer* L, int n, std::vector<WWItem>& items) {
 extern "C" size_t dl_wino_wgrad3x3_batch_workspace_bytes(const dl_wgrad_layer* layers, int32_t n) {
   std::vector<WWItem> items;
   if (ww_batch_plan(layers, n, items)) return 0;
-  size_t floats = 0;
-  for (const auto& it : items) floats += ((size_t)(it.a.nslabs > 1 ? it.a.nslabs : 0) + 1) * 16 * it.a.K * it.a.C;
-  return floats * sizeof(float);
+  return dl_carve_workspace(items, nullptr, true, 0) * sizeof(float);
 }
 
 extern "C" int dl_wino_wgrad3x3_batch_nhwc_f32(const dl_wgrad_layer* layers, int32_t n, void* workspace, dl_stream stream) {
@@ -1335,49 +1299,27 @@ extern "C" int dl_wino_wgrad3x3_batch_nhwc_f32(const dl_wgrad_layer* layers, int
   for (int i = 0; i < n; ++i)
     if (!layers[i].x || !layers[i].g || !layers[i].dw) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_wino_wgrad3x3_batch_nhwc_f32: layer %d: null pointer", i);
   hipStream_t st = (hipStream_t)stream;
-  float* wsf = (float*)workspace;
-  for (auto& it : items) {                               // [slab partials (only when split)] [their sum]
-    const size_t plane = (size_t)16 * it.a.K * it.a.C;
-    if (it.a.nslabs > 1) { it.a.ws = wsf; wsf += (size_t)it.a.nslabs * plane; it.usum = wsf; wsf += plane; }
-    else { it.a.ws = wsf; it.usum = wsf; wsf += plane; }  // a single slab IS the sum
-  }
-  for (int rag = 0; rag < 2; ++rag) {
-    std::vector<const WWItem*> grp;
-    for (const auto& it : items) if (it.rag == rag) grp.push_back(&it);
-    if (grp.empty()) continue;
-    std::stable_sort(grp.begin(), grp.end(), [](const WWItem* x, const WWItem* y) { return x->a.chunks_per_slab > y->a.chunks_per_slab; });
+  dl_carve_workspace(items, (float*)workspace, true, 0);  // [slab partials (only when split)] [their sum]: a single slab IS the sum
+  std::vector<const WWItem*> grp;
+  for (int rag : kWWKeys) {
     WWBatchArgs b{};
-    b.n = (int)grp.size();
-    int wgs = 0;
-    double flop = 0, bytes = 0;
-    for (int i = 0; i < b.n; ++i) {
-      b.layer[i] = grp[i]->a;
-      b.first_wg[i] = wgs;
-      wgs += grp[i]->tiles * grp[i]->a.nslabs;
-      flop += grp[i]->flop; bytes += grp[i]->bytes;
-    }
-    b.first_wg[b.n] = wgs;
+    const DlGroupWork w = dl_fill_group(items, rag, [](const WWItem& it) { return it.p.chunks_per_slab; }, b, grp);
+    if (!b.n) continue;
     const WWArgs& f = grp[0]->a;
-    const DlProfTag tag{"k_wino_wgrad", b.n > 1 ? "wgrad-batch" : "wgrad", f.N, f.H, f.W, f.C, f.K, 3, 1, 1, flop, bytes};
-    if (rag) DL_LAUNCH(tag, k_wino_wgrad_batch<true>, dim3(wgs), dim3(WW_THREADS), st, b);
-    else DL_LAUNCH(tag, k_wino_wgrad_batch<false>, dim3(wgs), dim3(WW_THREADS), st, b);
+    const DlProfTag tag{"k_wino_wgrad", b.n > 1 ? "wgrad-batch" : "wgrad", f.N, f.H, f.W, f.C, f.K, 3, 1, 1, w.flop, w.bytes};
+    if (rag) DL_LAUNCH(tag, k_wino_wgrad_batch<true>, dim3(w.wgs), dim3(WW_THREADS), st, b);
+    else DL_LAUNCH(tag, k_wino_wgrad_batch<false>, dim3(w.wgs), dim3(WW_THREADS), st, b);
     for (int i = 0; i < b.n; ++i) DL_PLAN_NOTE("slabs=%d", b.layer[i].nslabs);
   }
   WWPostArgs sum{}, out{};
-  int sum_blocks = 0, out_blocks = 0;
-  for (const auto& it : items) {
-    if (it.a.nslabs > 1) {
-      sum.src[sum.n] = it.a.ws; sum.dst[sum.n] = it.usum; sum.K[sum.n] = it.a.K; sum.C[sum.n] = it.a.C; sum.nslabs[sum.n] = it.a.nslabs;
-      sum.first_block[sum.n] = sum_blocks;
-      sum_blocks += (int)(((size_t)16 * it.a.K * it.a.C / 4 + 255) / 256);
-      ++sum.n;
-    }
-    out.src[out.n] = it.usum; out.dst[out.n] = it.dw; out.K[out.n] = it.a.K; out.C[out.n] = it.a.C;
-    out.first_block[out.n] = out_blocks;
-    out_blocks += (int)(((size_t)it.a.K * it.a.C + 255) / 256);
-    ++out.n;
-  }
-  sum.first_block[sum.n] = sum_blocks; out.first_block[out.n] = out_blocks;
+  const int sum_blocks = dl_fill_post(items, true, 256, sum, [](WWPostArgs& t, int j, const WWItem& it) {
+    t.src[j] = it.part; t.dst[j] = it.sum; t.K[j] = it.a.K; t.C[j] = it.a.C; t.nslabs[j] = it.p.nslabs;
+    return it.plane / 4;
+  });
+  const int out_blocks = dl_fill_post(items, false, 256, out, [](WWPostArgs& t, int j, const WWItem& it) {
+    t.src[j] = it.sum; t.dst[j] = it.dw; t.K[j] = it.a.K; t.C[j] = it.a.C;
+    return (size_t)it.a.K * it.a.C;
+  });
   if (sum.n) DL_LAUNCH_PLAIN(k_wino_wgrad_sum_batch, dim3(sum_blocks), dim3(256), st, sum);
   DL_LAUNCH_PLAIN(k_wino_wgrad_out_batch, dim3(out_blocks), dim3(256), st, out);
   return dl_check_launch("dl_wino_wgrad3x3_batch_nhwc_f32");
@@ -1392,10 +1334,7 @@ struct SWSumArgs {
   int n;
 };
 __global__ __launch_bounds__(256) void k_wino_wgrad_strided_sum_batch(SWSumArgs b) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < SW_ITEMS; ++i)
-    if (i < b.n && (int)blockIdx.x >= b.first_block[i]) l = i;
+  const int l = dl_table_slot<SW_ITEMS>(b.first_block, b.n, (int)blockIdx.x);
   wino_wgrad_sum_body(b.src[l], b.nslabs[l], (size_t)b.count4[l], b.dst[l], (size_t)((int)blockIdx.x - b.first_block[l]) * 256 + threadIdx.x);
 }
 // dw [K][3][3][C] of the layer from the summed live planes: uo [4][3][K][C] (odd pixels: b = 0, 1, 2), ue [4][2][K][C] (even pixels: b = 1, 2).
@@ -1413,10 +1352,7 @@ __device__ __forceinline__ float sw_gt(int rr, float u0, float u1, float u2, flo
   return rr == 0 ? u0 + 0.5f * (u1 + u2) : rr == 1 ? 0.5f * (u1 - u2) : 0.5f * (u1 + u2) + u3;
 }
 __global__ __launch_bounds__(256) void k_wino_wgrad_strided_out_batch(SWOutArgs b) {
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < DL_WGRAD_BATCH; ++i)
-    if (i < b.n && (int)blockIdx.x >= b.first_block[i]) l = i;
+  const int l = dl_table_slot<DL_WGRAD_BATCH>(b.first_block, b.n, (int)blockIdx.x);
   const int K = b.K[l], C = b.C[l];
   const size_t i = (size_t)((int)blockIdx.x - b.first_block[l]) * 256 + threadIdx.x;
   if (i >= (size_t)K * C) return;
@@ -1458,10 +1394,10 @@ namespace {
 // An even-pixel block runs 16 of the odd-pixel block's 24 MFMAs per chunk, with the same DMA, barriers and per-column side work: the plan
 // weighs its chunks 3/4 (between the 2/3 of the matrix work alone and the 0.84-0.89 that dropping a quarter of k_wino_conv's planes left
 // of its time, profiles/strided_wino_harness.txt).
-struct SWItem {
-  WWArgs a;              // pair view; ws / nslabs / chunks_per_slab of this item
-  float* usum;
-  int odd, layer, tiles, planes;
+struct SWItem : DlBatchItem {
+  WWArgs a;              // pair view
+  int odd, layer, planes;
+  WWArgs args() const { WWArgs r = a; r.ws = part; r.chunks_per_slab = p.chunks_per_slab; r.nslabs = p.nslabs; return r; }
 };
 bool sw_all12() {
   static const bool on = [] { const char* e = getenv("DL_SWGRAD_ALL12"); return e && e[0] == '1'; }();
@@ -1482,28 +1418,22 @@ int sw_batch_plan(const dl_wgrad_layer* L, int n, std::vector<SWItem>& items) {
       return dl_fail(DL_ERR_UNSUPPORTED, "%s: layer %d: N %d with H=%d W=%d C=%d K=%d (positive, below 2^31 elements and 2^30 per sample)", me, i, l.N, l.H, l.W, l.C, l.K);
   }
   items.resize(2 * n);
-  std::vector<int> tl(2 * n), ch(2 * n), ns(2 * n);
   for (int i = 0; i < n; ++i) {
     const dl_wgrad_layer& l = L[i];
     const int chunks = l.N * (l.H / 2) * (l.W / 32);
     for (int odd = 1; odd >= 0; --odd) {
       SWItem& it = items[2 * i + (1 - odd)];
       it.a = WWArgs{(const float*)l.x, (const float*)l.g, nullptr, l.N, l.H, l.W / 2, 2 * l.C, l.K, 0, 0};
-      it.usum = nullptr; it.odd = odd; it.layer = i;
-      it.tiles = (l.K / 64) * (l.C / 64);
+      it.odd = odd; it.layer = i; it.key = 0;              // one launch with both bodies
       it.planes = odd || sw_all12() ? 12 : 8;
-      tl[2 * i + (1 - odd)] = it.tiles;
-      ch[2 * i + (1 - odd)] = it.planes == 12 ? chunks : (3 * chunks + 3) / 4;
+      it.plane = (size_t)it.planes * l.K * l.C;
+      it.p = DlSlabPlan{(l.K / 64) * (l.C / 64), chunks, it.planes == 12 ? chunks : (3 * chunks + 3) / 4, 0, 0};
+      // the live planes' multiply-adds: 2 . {12 | 8} . tiles . 64 . 64 per block; the layer's bytes counted once, with its odd item
+      it.flop = 2.0 * it.planes * (double)l.N * (l.H / 2) * (l.W / 4) * 64.0 * 64.0 * it.p.tiles;
+      it.bytes = odd ? 4.0 * ((double)l.N * l.H * (l.W / 2) * (2 * l.C + l.K) + 9.0 * l.C * l.K) : 0.0;
     }
   }
-  dl_plan_batch(tl.data(), ch.data(), 2 * n, 256, 10, ns.data());                      // one 512-thread workgroup per CU
-  for (int j = 0; j < 2 * n; ++j) {
-    SWItem& it = items[j];
-    const int chunks = it.a.N * (it.a.H / 2) * (it.a.W / 16);
-    const int want = ns[j] < chunks ? ns[j] : chunks;
-    it.a.chunks_per_slab = (chunks + want - 1) / want;
-    it.a.nslabs = (chunks + it.a.chunks_per_slab - 1) / it.a.chunks_per_slab;
-  }
+  dl_plan_slabs(items, {0}, 256, 10);                      // one 512-thread workgroup per CU
   return DL_OK;
 }
 }  // namespace
@@ -1512,9 +1442,7 @@ int sw_batch_plan(const dl_wgrad_layer* L, int n, std::vector<SWItem>& items) {
 extern "C" size_t dl_wino_strided_wgrad3x3_batch_workspace_bytes(const dl_wgrad_layer* layers, int32_t n) {
   std::vector<SWItem> items;
   if (sw_batch_plan(layers, n, items)) return 0;
-  size_t floats = 0;
-  for (const auto& it : items) floats += ((size_t)(it.a.nslabs > 1 ? it.a.nslabs : 0) + 1) * it.planes * it.a.K * (it.a.C / 2);
-  return floats * sizeof(float);
+  return dl_carve_workspace(items, nullptr, true, 0) * sizeof(float);
 }
 
 extern "C" int dl_wino_strided_wgrad3x3_batch_nhwc_f32(const dl_wgrad_layer* layers, int32_t n, void* workspace, dl_stream stream) {
@@ -1525,57 +1453,32 @@ extern "C" int dl_wino_strided_wgrad3x3_batch_nhwc_f32(const dl_wgrad_layer* lay
   for (int i = 0; i < n; ++i)
     if (!layers[i].x || !layers[i].g || !layers[i].dw) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_wino_strided_wgrad3x3_batch_nhwc_f32: layer %d: null pointer", i);
   hipStream_t st = (hipStream_t)stream;
-  float* wsf = (float*)workspace;
-  for (auto& it : items) {                               // [slab partials (only when split)] [their sum]
-    const size_t plane = (size_t)it.planes * it.a.K * (it.a.C / 2);
-    if (it.a.nslabs > 1) { it.a.ws = wsf; wsf += (size_t)it.a.nslabs * plane; it.usum = wsf; wsf += plane; }
-    else { it.a.ws = wsf; it.usum = wsf; wsf += plane; }  // a single slab IS the sum
-  }
+  dl_carve_workspace(items, (float*)workspace, true, 0);  // [slab partials (only when split)] [their sum]: a single slab IS the sum
   std::vector<const SWItem*> grp;
-  for (const auto& it : items) grp.push_back(&it);
-  std::stable_sort(grp.begin(), grp.end(), [](const SWItem* x, const SWItem* y) {        // by decreasing time per workgroup (chunks x MFMAs per chunk)
-    return x->a.chunks_per_slab * (x->planes / 4 + 1) > y->a.chunks_per_slab * (y->planes / 4 + 1);
-  });
   SWBatchArgs b{};
-  b.n = (int)grp.size();
-  int wgs = 0;
-  double flop = 0, bytes = 0;
-  for (int i = 0; i < b.n; ++i) {
-    const WWArgs& a = grp[i]->a;
-    b.item[i] = a;
-    b.odd[i] = grp[i]->odd;
-    b.first_wg[i] = wgs;
-    wgs += grp[i]->tiles * a.nslabs;
-    // the live planes' multiply-adds: 2 . {12 | 8} . tiles . 64 . 64 per block
-    flop += 2.0 * grp[i]->planes * (double)a.N * (a.H / 2) * (a.W / 2) * 64.0 * 64.0 * grp[i]->tiles;
-    if (grp[i]->odd) bytes += 4.0 * ((double)a.N * a.H * a.W * (a.C + a.K) + 9.0 * (a.C / 2) * a.K);
-  }
-  b.first_wg[b.n] = wgs;
+  // by decreasing time per workgroup (chunks x MFMAs per chunk)
+  const DlGroupWork w = dl_fill_group(items, 0, [](const SWItem& it) { return it.p.chunks_per_slab * (it.planes / 4 + 1); }, b, grp);
+  for (int i = 0; i < b.n; ++i) b.odd[i] = grp[i]->odd;
   const dl_wgrad_layer& f = layers[grp[0]->layer];
-  const DlProfTag tag{"k_wino_wgrad_strided", n > 1 ? "wgrad-batch" : "wgrad", f.N, f.H, f.W, f.C, f.K, 3, 1, 2, flop, bytes};
-  if (sw_all12()) DL_LAUNCH(tag, k_wino_wgrad_strided_batch<true>, dim3(wgs), dim3(WW_THREADS), st, b);
-  else DL_LAUNCH(tag, k_wino_wgrad_strided_batch<false>, dim3(wgs), dim3(WW_THREADS), st, b);
-  for (int i = 0; i < b.n; ++i) DL_PLAN_NOTE("%s slabs=%d", b.odd[i] ? "odd" : "even", b.item[i].nslabs);
+  const DlProfTag tag{"k_wino_wgrad_strided", n > 1 ? "wgrad-batch" : "wgrad", f.N, f.H, f.W, f.C, f.K, 3, 1, 2, w.flop, w.bytes};
+  if (sw_all12()) DL_LAUNCH(tag, k_wino_wgrad_strided_batch<true>, dim3(w.wgs), dim3(WW_THREADS), st, b);
+  else DL_LAUNCH(tag, k_wino_wgrad_strided_batch<false>, dim3(w.wgs), dim3(WW_THREADS), st, b);
+  for (int i = 0; i < b.n; ++i) DL_PLAN_NOTE("%s slabs=%d", b.odd[i] ? "odd" : "even", b.layer[i].nslabs);
   SWSumArgs sum{};
-  SWOutArgs out{};
-  int sum_blocks = 0, out_blocks = 0;
-  for (const auto& it : items) {
-    if (it.a.nslabs > 1) {
-      const size_t count4 = (size_t)it.planes * it.a.K * (it.a.C / 2) / 4;
-      sum.src[sum.n] = it.a.ws; sum.dst[sum.n] = it.usum; sum.count4[sum.n] = (int)count4; sum.nslabs[sum.n] = it.a.nslabs;
-      sum.first_block[sum.n] = sum_blocks;
-      sum_blocks += (int)((count4 + 255) / 256);
-      ++sum.n;
-    }
-    if (it.odd) out.uo[it.layer] = it.usum; else out.ue[it.layer] = it.usum;
-  }
+  const int sum_blocks = dl_fill_post(items, true, 256, sum, [](SWSumArgs& t, int j, const SWItem& it) {
+    t.src[j] = it.part; t.dst[j] = it.sum; t.count4[j] = (int)(it.plane / 4); t.nslabs[j] = it.p.nslabs;
+    return it.plane / 4;
+  });
+  SWOutArgs out{};                                         // one entry per LAYER, from the sums of its two items
+  int out_blocks = 0;
+  for (const auto& it : items) (it.odd ? out.uo : out.ue)[it.layer] = it.sum;
   for (int i = 0; i < n; ++i) {
     out.dw[i] = layers[i].dw; out.K[i] = layers[i].K; out.C[i] = layers[i].C;
     out.first_block[i] = out_blocks;
     out_blocks += (int)(((size_t)layers[i].K * layers[i].C + 255) / 256);
   }
   out.n = n; out.eb = sw_all12() ? 3 : 2;
-  sum.first_block[sum.n] = sum_blocks; out.first_block[n] = out_blocks;
+  out.first_block[n] = out_blocks;
   if (sum.n) DL_LAUNCH_PLAIN(k_wino_wgrad_strided_sum_batch, dim3(sum_blocks), dim3(256), st, sum);
   DL_LAUNCH_PLAIN(k_wino_wgrad_strided_out_batch, dim3(out_blocks), dim3(256), st, out);
   return dl_check_launch("dl_wino_strided_wgrad3x3_batch_nhwc_f32");
