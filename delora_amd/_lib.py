@@ -22,9 +22,18 @@ class SensorStruct(ctypes.Structure):
                 ("vfov0", ctypes.c_double), ("vfov1", ctypes.c_double)]
 
 
+class RecordLayout(ctypes.Structure):
+    """``dl_record_layout`` of include/delora_hip.h: fp32 x, y, z at byte offsets of ``point_step``-byte records, and the filter."""
+    _fields_ = [("point_step", ctypes.c_int32), ("off_x", ctypes.c_int32), ("off_y", ctypes.c_int32), ("off_z", ctypes.c_int32),
+                ("filter", ctypes.c_uint32), ("min_range", ctypes.c_float)]
+
+
+RECORDS_DROP_ZERO, RECORDS_MIN_RANGE = 1, 2          # DL_RECORDS_* of include/delora_hip.h
+
 _vp, _i32, _i64, _u32, _f32, _sz = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
                                     ctypes.c_float, ctypes.c_size_t)
 _SP = ctypes.POINTER(SensorStruct)
+_RP = ctypes.POINTER(RecordLayout)
 
 # name -> (restype, argtypes); mirrors the declarations of include/delora_hip.h one to one
 SIGNATURES = {
@@ -32,6 +41,8 @@ SIGNATURES = {
     "dl_last_error": (ctypes.c_char_p, []),
     "dl_project_workspace_bytes": (_sz, [_i32, _i32, _i32, _i64, _i32]),
     "dl_project": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dl_project_records_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dl_project_records": (_i32, [_vp, _i64, _RP, _vp, _i32, _i32, _SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dl_reproject_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dl_reproject": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _SP, _vp, _vp, _vp, _vp, _vp]),
     "dl_normals": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
@@ -133,6 +144,7 @@ SIGNATURES = {
     "dl_pose_net_forward": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "dl_odometry_workspace_bytes": (_sz, [_vp, _SP, _i32, _i32, _i32]),
     "dl_odometry_push": (_i32, [_vp, _vp, _SP, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dl_odometry_push_records": (_i32, [_vp, _vp, _SP, _vp, _i32, _RP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dl_profile_begin": (_i32, [_i32, ctypes.c_char_p]),
     "dl_profile_end": (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "dl_profile_pause": (_i32, [_i32]),

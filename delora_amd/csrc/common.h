@@ -105,6 +105,9 @@ int dl_check_launch(const char* what);
 // order of decreasing slab size, each to the first free slot -- plus the partial traffic is smallest.  Memoised per shape set.
 void dl_plan_batch(const int* tiles, const int* chunks, int n, int machines, int partial_cost, int* nslabs);
 int dl_fill_words(void* p, uint32_t value, size_t n_words, hipStream_t st);   // abi.hip: memset as a kernel (graph-safe)
+// project.hip: the refusals of a record layout (include/delora_hip.h, dl_project_records), shared with dl_odometry_push_records so
+// that it refuses before its first launch too.  DL_OK or dl_fail's code, the text starting with `who`.
+int dl_record_layout_check(const char* who, const void* records, const dl_record_layout* layout);
 
 // Launch profiler (abi.hip; dl_profile_begin / dl_profile_end of the C ABI): while a profile is open, every launch that goes
 // through DL_LAUNCH carries a pair of HIP events that receive the kernel's own begin / end timestamps (hipExtLaunchKernelGGL,

@@ -307,3 +307,32 @@ extern "C" int dl_odometry_push(const dl_pose_net* net, const void* prepared, co
   if (!image_prev) return DL_OK;
   return pose_forward(who, net, p, prepared, image_prev, (int64_t)4 * H * W, image_cur, (int64_t)4 * H * W, 1, H, W, workspace, translation, quaternion, T, stream);
 }
+
+/* see include/delora_hip.h */
+extern "C" int dl_odometry_push_records(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records, int32_t n_records,
+                                        const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur, void* workspace,
+                                        float* translation, float* quaternion, float* T, dl_stream stream) {
+  const char* who = "dl_odometry_push_records";
+  if (int rc = odometry_check(who, net, sensor)) return rc;
+  const int H = sensor->H, W = sensor->W;
+  if (!offs || !image_cur || !workspace || !layout || (!records && n_records > 0))
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument (records, layout, offs, image_cur, workspace)", who);
+  if (n_records < 0) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad sizes n_records=%d", who, n_records);
+  if (((uintptr_t)workspace & (kAlign - 1))) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: workspace must be 256-byte aligned", who);
+  if (((uintptr_t)image_cur & 3) || ((uintptr_t)offs & 3)) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: image_cur / offs are not 4-byte aligned", who);
+  if (int rc = dl_record_layout_check(who, records, layout)) return rc;
+  if (image_prev)
+    if (int rc = forward_args(who, prepared, image_prev, (int64_t)4 * H * W, image_cur, (int64_t)4 * H * W, H, W, workspace, translation, quaternion, T)) return rc;
+  // workspace: the forward's (B = 1) | pix2pt [H*W] int32 | the key plane -- dl_odometry_workspace_bytes with max_points = 0
+  const PosePlan p = pose_plan(net, 1, H, W);
+  char* const ws = (char*)workspace;
+  int32_t* pix2pt = (int32_t*)(ws + p.total);
+  void* project_ws = ws + p.total + align_up((size_t)H * W * 4);
+  hipLaunchKernelGGL(k_single_scan_offsets, dim3(1), dim3(64), 0, (hipStream_t)stream, offs, n_records);
+  if (int rc = dl_check_launch(who)) return rc;
+  if (int rc = at_layer(who, "projection", -1, dl_project_records(records, n_records, layout, offs, 1, n_records, sensor, image_cur, nullptr, pix2pt,
+                                                                  project_ws, nullptr, nullptr, stream)))
+    return rc;
+  if (!image_prev) return DL_OK;
+  return pose_forward(who, net, p, prepared, image_prev, (int64_t)4 * H * W, image_cur, (int64_t)4 * H * W, 1, H, W, workspace, translation, quaternion, T, stream);
+}

@@ -180,3 +180,202 @@ extern "C" int dl_project(const float* pts, int64_t pts_cs, int64_t n_cols, cons
                      (float4*)packed, (float4*)packed_aux, pix2pt, kept);
   return dl_check_launch("dl_project");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Records flavour: the scan as a sensor or a driver delivers it -- n records of point_step bytes with fp32 x, y, z at byte offsets
+// (a KITTI .bin file: 16 / 0, 4, 8; a PointCloud2 message: its point_step and field offsets) -- and the reference node's filter
+// (src/ros_utils/odometry_publisher.py:95-97) applied inside the vote.  The winner of a pixel is the smallest (range bits, index
+// within the scan): a record that does not vote leaves every other record's key as it is, so skipping it gives the image that
+// compacting the list first gives, with record indices in pix2pt instead of list positions.  No compaction pass, and no staging
+// records either: the upper half of a winning key IS the range the vote computed, and resolve gathers x, y, z of the one winning
+// record per occupied pixel from the record buffer itself (they share a 64-byte line for every step the layout check admits below
+// 64).  HBM traffic per scan: the vote reads point_step * N bytes where the planar vote reads 12 N and writes 16 N.
+// image coordinates of one point, the expressions of k_project_scatter (kept there word for word: its code is not touched): atan2f
+// unless a coordinate lies near a rounding boundary
+__device__ __forceinline__ void project_uv(float x, float y, float z, const SensorK& sen, float& u, float& v) {
+  u = coord_u_fast(x, y, sen);
+  v = coord_v_fast(x, y, z, sen);
+  if (near_rounding_boundary(u, sen.tol_u) || near_rounding_boundary(v, sen.tol_v)) {
+    u = coord_u(x, y, sen);
+    v = coord_v(x, y, z, sen);
+  }
+}
+
+// the vote of k_project_scatter: point i (index within its scan) with range r at coordinates (u, v) on its scan's key plane
+__device__ __forceinline__ void project_vote(float u, float v, float r, int i, const SensorK& sen, unsigned long long* __restrict__ kp) {
+  const float ru = rintf(u), rv = rintf(v);   // torch.round: half to even
+  if (ru <= sen.wm1f && ru >= 0.0f && rv <= sen.hm1f && rv >= 0.0f) {   // projection.py:74-75
+    const unsigned long long key = ((unsigned long long)__float_as_uint(r) << 32) | (unsigned int)i;
+    atomicMin(&kp[(int)rv * sen.W + (int)ru], key);
+  }
+}
+
+struct RecordK {
+  int step, wx, wy, wz;     // record length in bytes, x / y / z as dword offsets within a record
+  unsigned int filter;
+  float min_range;
+};
+
+// np.linalg.norm(xyz, axis=0) of the reference's filter: sqrt((x*x + y*y) + z*z), every operation rounded to fp32, nothing fused.
+// NOT norm3f: near the 0.3 m threshold the two fall on different sides for ~1 % of the points within a few ulp of it.  The pragma keeps the three
+// operations apart under any -ffp-contract setting; sqrtf is correctly rounded (common.h: __fsqrt_rn is not, it lowers to the
+// native approximation here, and __fmul_rn / __fadd_rn are plain operators that a contracting build would fuse all the same).
+__device__ __forceinline__ float range_np(float x, float y, float z) {
+#pragma clang fp contract(off)
+  const float xx = x * x;
+  const float yy = y * y;
+  const float zz = z * z;
+  const float s2 = xx + yy;
+  const float s3 = s2 + zz;
+  return sqrtf(s3);
+}
+
+// does a record take part?  -0.0 counts as zero, NaN does not; a NaN range or a NaN comparison drops the record
+__device__ __forceinline__ bool record_passes(float x, float y, float z, const RecordK& lay) {
+  if ((lay.filter & DL_RECORDS_DROP_ZERO) && !(x != 0.0f && y != 0.0f && z != 0.0f)) return false;
+  if ((lay.filter & DL_RECORDS_MIN_RANGE) && !(range_np(x, y, z) > lay.min_range)) return false;
+  return true;
+}
+
+// word k of a 16-byte record (k is uniform: three selects, no indexed register file)
+__device__ __forceinline__ float record_word(const float4& q, int k) { return k == 0 ? q.x : k == 1 ? q.y : k == 2 ? q.z : q.w; }
+
+// VEC16: 16-byte records on a 16-byte aligned base, one dwordx4 load per lane; else three dword loads at the record stride
+template <bool VEC16>
+__global__ __launch_bounds__(DL_BLOCK) void k_project_records_scatter(
+    const float* __restrict__ rec, int64_t n_records, RecordK lay, const int32_t* __restrict__ offs, int S, int G, SensorK sen,
+    unsigned long long* __restrict__ keys, int32_t* __restrict__ n_pass) {
+  int s, chunk;
+  if (!project_block(S, G, s, chunk)) return;
+  const int n0 = offs[s];
+  const int n = offs[s + 1] - n0;
+  unsigned long long* kp = keys + (size_t)s * sen.HW;
+  const int stride = (G < 0 ? -G : G) * DL_BLOCK;
+  const int64_t step_w = lay.step >> 2;
+  int passed = 0;
+  for (int i = chunk * DL_BLOCK + threadIdx.x; i < n; i += stride) {
+    const int64_t g = (int64_t)n0 + i;
+    if (g < 0 || g >= n_records) continue;      // offsets that disagree with the record count: no load, no vote
+    float x, y, z;
+    if (VEC16) {
+      const float4 q = reinterpret_cast<const float4*>(rec)[g];
+      x = record_word(q, lay.wx); y = record_word(q, lay.wy); z = record_word(q, lay.wz);
+    } else {
+      const float* p = rec + g * step_w;
+      x = p[lay.wx]; y = p[lay.wy]; z = p[lay.wz];
+    }
+    if (!record_passes(x, y, z, lay)) continue;
+    ++passed;
+    const float r = norm3f(x, y, z);            // the key's range is dl_project's (fused), whatever the filter compared
+    float u, v;
+    project_uv(x, y, z, sen, u, v);
+    project_vote(u, v, r, i, sen, kp);
+  }
+  if (n_pass) {   // optional statistic: one atomic per workgroup
+    __shared__ int s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+#pragma unroll
+    for (int o = DL_WAVE / 2; o > 0; o >>= 1) passed += __shfl_xor(passed, o, DL_WAVE);
+    if ((threadIdx.x & (DL_WAVE - 1)) == 0 && passed) atomicAdd(&s_cnt, passed);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(&n_pass[s], s_cnt);
+  }
+}
+
+__global__ __launch_bounds__(DL_BLOCK) void k_project_records_resolve(
+    const float* __restrict__ rec, RecordK lay, const int32_t* __restrict__ offs, int S, int G, SensorK sen,
+    const unsigned long long* __restrict__ keys, float* __restrict__ image4, float4* __restrict__ packed, int32_t* __restrict__ pix2pt,
+    int32_t* __restrict__ kept) {
+  int s, chunk;
+  if (!project_block(S, G, s, chunk)) return;
+  const int px = chunk * DL_BLOCK + threadIdx.x;
+  const int HW = sen.HW;
+  bool occupied = false;
+  if (px < HW) {
+    const unsigned long long key = keys[(size_t)s * HW + px];
+    float* img = image4 + (size_t)s * 4 * HW + px;
+    occupied = key != ~0ull;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    int idx = -1;
+    if (occupied) {
+      idx = (int)(unsigned int)(key & 0xffffffffu);
+      const float* q = rec + ((int64_t)offs[s] + idx) * (int64_t)(lay.step >> 2);   // a record that voted: inside the buffer
+      p = make_float4(q[lay.wx], q[lay.wy], q[lay.wz], __uint_as_float((unsigned int)(key >> 32)));
+    }
+    img[0] = p.x; img[HW] = p.y; img[2 * HW] = p.z; img[3 * HW] = p.w;
+    if (packed) packed[(size_t)s * HW + px] = p;
+    pix2pt[(size_t)s * HW + px] = idx;
+  }
+  if (kept) {   // optional statistic: one atomic per workgroup
+    __shared__ int s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const unsigned long long m = __ballot(occupied);
+    if ((threadIdx.x & (DL_WAVE - 1)) == 0 && m) atomicAdd(&s_cnt, (int)__popcll(m));
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(&kept[s], s_cnt);
+  }
+}
+
+/* see common.h */
+int dl_record_layout_check(const char* who, const void* records, const dl_record_layout* layout) {
+  if (!layout) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null layout", who);
+  if (layout->filter & ~(DL_RECORDS_DROP_ZERO | DL_RECORDS_MIN_RANGE))
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: unknown bit in layout.filter=0x%x", who, layout->filter);
+  const int step = layout->point_step;
+  if (step < 12 || step > 256 || (step & 3))
+    return dl_fail(DL_ERR_UNSUPPORTED, "%s: layout.point_step=%d is not a multiple of 4 in 12..256", who, step);
+  const int off[3] = {layout->off_x, layout->off_y, layout->off_z};
+  const char* name[3] = {"off_x", "off_y", "off_z"};
+  for (int k = 0; k < 3; ++k) {
+    if (off[k] < 0 || (off[k] & 3) || off[k] + 4 > step)
+      return dl_fail(DL_ERR_UNSUPPORTED, "%s: layout.%s=%d is not a multiple of 4 in 0..point_step-4 (point_step=%d)", who, name[k], off[k], step);
+    for (int j = 0; j < k; ++j)
+      if (off[j] == off[k]) return dl_fail(DL_ERR_UNSUPPORTED, "%s: layout.%s=%d repeats layout.%s", who, name[k], off[k], name[j]);
+  }
+  if ((layout->filter & DL_RECORDS_MIN_RANGE) && !(fabsf(layout->min_range) <= 3.402823466e38f))
+    return dl_fail(DL_ERR_UNSUPPORTED, "%s: layout.min_range is not finite", who);
+  if ((uintptr_t)records & 3) return dl_fail(DL_ERR_UNSUPPORTED, "%s: records must be 4-byte aligned (no misaligned device loads)", who);
+  return DL_OK;
+}
+
+extern "C" size_t dl_project_records_workspace_bytes(int32_t S, int32_t H, int32_t W) {
+  if (S <= 0 || H <= 0 || W <= 0) return 0;
+  return project_keys_bytes(S, H, W);
+}
+
+extern "C" int dl_project_records(const void* records, int64_t n_records, const dl_record_layout* layout, const int32_t* offs, int32_t S,
+                                  int32_t max_n, const dl_sensor* sensor, float* image4, float* packed, int32_t* pix2pt, void* workspace,
+                                  int32_t* kept, int32_t* n_pass, dl_stream stream) {
+  const char* who = "dl_project_records";
+  if ((!records && n_records > 0) || !layout || !offs || !sensor || !image4 || !pix2pt || !workspace)
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
+  if (S <= 0 || sensor->H < 2 || sensor->W < 2 || max_n < 0 || n_records < 0)
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad sizes S=%d H=%d W=%d max_n=%d n_records=%lld", who, S, sensor->H, sensor->W, max_n,
+                   (long long)n_records);
+  if ((uintptr_t)workspace & 15) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  if (int rc = dl_record_layout_check(who, records, layout)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const SensorK sen = make_sensor(sensor);
+  const RecordK lay = {layout->point_step, layout->off_x >> 2, layout->off_y >> 2, layout->off_z >> 2, layout->filter, layout->min_range};
+  const float* rec = (const float*)records;
+  unsigned long long* keys = (unsigned long long*)workspace;   // the workspace is the key plane [S][H*W] uint64 and nothing else
+  dl_fill_words(keys, 0xffffffffu, (size_t)S * sen.HW * 2, st);
+  if (kept) dl_fill_words(kept, 0u, (size_t)S, st);
+  if (n_pass) dl_fill_words(n_pass, 0u, (size_t)S, st);
+  if (max_n > 0 && n_records > 0) {
+    int G = (max_n + DL_BLOCK - 1) / DL_BLOCK;
+    if (G > 1024) G = 1024;
+    if (lay.step == 16 && !((uintptr_t)records & 15))
+      hipLaunchKernelGGL(k_project_records_scatter<true>, dim3(project_grid(S, G)), dim3(DL_BLOCK), 0, st, rec, n_records, lay, offs, S,
+                         project_garg(S, G), sen, keys, n_pass);
+    else
+      hipLaunchKernelGGL(k_project_records_scatter<false>, dim3(project_grid(S, G)), dim3(DL_BLOCK), 0, st, rec, n_records, lay, offs, S,
+                         project_garg(S, G), sen, keys, n_pass);
+  }
+  const int G = (sen.HW + DL_BLOCK - 1) / DL_BLOCK;
+  hipLaunchKernelGGL(k_project_records_resolve, dim3(project_grid(S, G)), dim3(DL_BLOCK), 0, st, rec, lay, offs, S, project_garg(S, G), sen,
+                     (const unsigned long long*)keys, image4, (float4*)packed, pix2pt, kept);
+  return dl_check_launch(who);
+}

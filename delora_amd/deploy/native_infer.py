@@ -183,7 +183,8 @@ class NativePoseNet(object):
 class NativeOdometry(object):
     """``dl_odometry_push`` with its buffers: two ping-pong images, the offsets vector, the workspace (grown when a larger scan
     arrives) and the three outputs.  ``push(points [3,N])`` returns None for the first scan, then (translation [1,3], quaternion [1,4],
-    T [1,4,4]) -- tensors that the next push overwrites.  ``image_t_1`` / ``image_t`` are the images of the last pair."""
+    T [1,4,4]) -- tensors that the next push overwrites.  ``image_t_1`` / ``image_t`` are the images of the last pair.
+    ``push_records(records, layout)`` is the same from raw point records (``dl_odometry_push_records``); the two may be mixed."""
 
     def __init__(self, model, sensor, max_points=1 << 17):
         self.pose = NativePoseNet(model, 1, sensor.H, sensor.W, own_workspace=False)     # (the forward's workspace is the head of this one's)
@@ -196,6 +197,8 @@ class NativeOdometry(object):
         self.max_points, self.workspace = 0, None
         self._reserve(max_points)
         self.cur, self.count = 0, 0
+        # push_records from the host: two alternating page-locked staging buffers with the event behind their last transfer, one device buffer
+        self._stage, self._stage_np, self._stage_event, self._stage_next, self._records = [None, None], [None, None], [None, None], 0, None
 
     def _reserve(self, n_points):
         if self.workspace is not None and n_points <= self.max_points:
@@ -228,6 +231,74 @@ class NativeOdometry(object):
                                              p(self.T), ring_conv._stream()), "dl_odometry_push")
         self.count += 1
         return (self.translation, self.quaternion, self.T) if prev is not None else None
+
+    def _upload(self, host):
+        """The bytes of a contiguous host array -> the kept device buffer, through one of two alternating page-locked staging buffers:
+        the host copy of message k+1 overlaps the transfer (and the push) of message k, and a staging buffer is overwritten only after
+        the event behind its last transfer (a single reused pinned buffer once let the next message overwrite a transfer
+        in flight).  Buffers grow on demand and are kept: nothing is allocated per push once they have grown."""
+        flat = host.reshape(-1).view(np.uint8)
+        n = int(flat.shape[0])
+        k = self._stage_next
+        self._stage_next = 1 - k
+        if self._stage[k] is None or self._stage[k].numel() < n:
+            if self._stage_event[k] is not None:
+                self._stage_event[k].synchronize()
+            self._stage[k] = torch.empty((max(n, 2 * (0 if self._stage[k] is None else self._stage[k].numel())),), dtype=torch.uint8, pin_memory=True)
+            self._stage_np[k] = self._stage[k].numpy()
+            self._stage_event[k] = torch.cuda.Event()
+        else:
+            self._stage_event[k].synchronize()
+        if self._records is None or self._records.numel() < n:
+            # (the old buffer goes back to the caching allocator, which keeps it for this stream's later work: stream-ordered reuse)
+            self._records = torch.empty((max(n, 2 * (0 if self._records is None else self._records.numel())),), dtype=torch.uint8,
+                                        device=self.pose.device)
+        np.copyto(self._stage_np[k][:n], flat)
+        self._records[:n].copy_(self._stage[k][:n], non_blocking=True)
+        self._stage_event[k].record()
+        return self._records, n
+
+    def push_records(self, records, layout):
+        """``push`` from raw point records (``dl_odometry_push_records``): ``layout`` is a ``_lib.RecordLayout``, filter included.
+        records: a CUDA 1-D ``uint8`` / ``float32`` tensor goes to the library as it is; a contiguous host ``numpy`` array -- any dtype
+        whose itemsize is ``point_step`` (a structured message), ``[N,C]`` fp32 with ``4*C == point_step``, or raw bytes -- is staged
+        and copied asynchronously.  Nothing is filtered, compacted or transposed on the host."""
+        why = why_layout_unsupported(layout)
+        if why is not None:
+            raise ValueError("push_records: " + why)
+        if torch.is_tensor(records):
+            if not records.is_cuda or records.dtype not in (torch.uint8, torch.float32) or records.dim() != 1 or not records.is_contiguous():
+                raise ValueError("records must be a contiguous 1-D uint8 or float32 CUDA tensor (or a host numpy array)")
+            buf, nbytes = records, records.numel() * records.element_size()
+        else:
+            if not isinstance(records, np.ndarray) or not records.flags.c_contiguous:
+                raise ValueError("records must be a C-contiguous numpy array (or a CUDA tensor)")
+            buf, nbytes = self._upload(records)
+        if nbytes % layout.point_step:
+            raise ValueError(f"{nbytes} bytes are not whole records of {layout.point_step} bytes")
+        if self.count:
+            self.cur = 1 - self.cur
+        prev = self.images[1 - self.cur] if self.count else None
+        p = ring_conv._ptr
+        _lib.check(self.lib.dl_odometry_push_records(self.pose._net_p, p(self.pose.prepared), ctypes.byref(self.sensor.struct), p(buf),
+                                                     nbytes // layout.point_step, ctypes.byref(layout), p(self.offs), p(prev), p(self.images[self.cur]),
+                                                     p(self.workspace), p(self.translation), p(self.quaternion), p(self.T), ring_conv._stream()),
+                   "dl_odometry_push_records")
+        self.count += 1
+        return (self.translation, self.quaternion, self.T) if prev is not None else None
+
+
+def why_layout_unsupported(layout):
+    """None when ``dl_project_records`` serves this ``_lib.RecordLayout``, else the reason (the C side's rule restated, so that a
+    caller can choose the host route before anything is copied)."""
+    step, offs = layout.point_step, (layout.off_x, layout.off_y, layout.off_z)
+    if step % 4 or not 12 <= step <= 256:
+        return f"point_step={step} is not a multiple of 4 in 12..256"
+    if any(o < 0 or o % 4 or o + 4 > step for o in offs) or len(set(offs)) != 3:
+        return f"offsets {offs} are not three distinct multiples of 4 inside a {step}-byte record"
+    if layout.filter & _lib.RECORDS_MIN_RANGE and not np.isfinite(layout.min_range):
+        return "min_range is not finite"
+    return None
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -88,7 +88,41 @@ def project(points, offsets, max_points, sensor, want_uv=False, want_kept=True, 
             "uv": uv}
 
 
-def normals(image4, half_rows=3, half_cols=5, epsilon_range=0.5, min_neighbors=10, want_packed=False):
+def record_layout(point_step, offsets, filter=0, min_range=0.0):
+    """A ``_lib.RecordLayout``: fp32 x, y, z at byte ``offsets`` of ``point_step``-byte records; ``filter`` = ``_lib.RECORDS_*`` bits."""
+    ox, oy, oz = (int(o) for o in offsets)
+    return _lib.RecordLayout(int(point_step), ox, oy, oz, int(filter), float(min_range))
+
+
+def project_records(records, offsets, max_points, sensor, layout, want_kept=True, want_packed=True):
+    """Range images of S scans given as raw point records (``dl_project_records``), the layout's filter applied inside the vote.
+    records: 1-D ``uint8`` or ``float32`` CUDA tensor holding whole records; offsets ``[S+1]`` int32 (device), in records.
+    Returns the dict of ``project`` (aux / packed_aux / uv None; pix2pt holds RECORD indices) plus n_pass ``[S]`` int32: the records
+    that took part."""
+    lib = _lib.load()
+    _require_cuda(records, offsets)
+    if records.dtype not in (torch.uint8, torch.float32) or records.dim() != 1 or not records.is_contiguous():
+        raise ValueError("records must be a contiguous 1-D uint8 or float32 tensor")
+    if offsets.dtype != torch.int32:
+        raise ValueError("offsets must be int32")
+    nbytes = records.numel() * records.element_size()
+    if layout.point_step <= 0 or nbytes % layout.point_step:
+        raise ValueError(f"{nbytes} bytes are not whole records of {layout.point_step} bytes")
+    S, H, W, dev = offsets.numel() - 1, sensor.H, sensor.W, records.device
+    image4 = torch.empty((S, 4, H, W), dtype=torch.float32, device=dev)
+    packed = torch.empty((S, H, W, 4), dtype=torch.float32, device=dev) if want_packed else None
+    pix2pt = torch.empty((S, H, W), dtype=torch.int32, device=dev)
+    kept = torch.empty((S,), dtype=torch.int32, device=dev) if want_kept else None
+    n_pass = torch.empty((S,), dtype=torch.int32, device=dev)
+    ws = torch.empty((lib.dl_project_records_workspace_bytes(S, H, W) // 8,), dtype=torch.int64, device=dev)
+    _lib.check(lib.dl_project_records(_ptr(records), nbytes // layout.point_step, ctypes.byref(layout), _ptr(offsets), S, int(max_points),
+                                      ctypes.byref(sensor.struct), _ptr(image4), _ptr(packed), _ptr(pix2pt), _ptr(ws), _ptr(kept),
+                                      _ptr(n_pass), _stream()), "dl_project_records")
+    return {"image4": image4, "aux": None, "packed": packed, "packed_aux": None, "pix2pt": pix2pt, "kept": kept, "uv": None,
+            "n_pass": n_pass}
+
+
+def normals(image4, half_rows=3,half_cols=5, epsilon_range=0.5, min_neighbors=10, want_packed=False):
     """Normals ``[S,3,H,W]`` of range images ``[S,>=3,H,W]`` (zero vector = no normal); with ``want_packed`` also the
     packed twin ``[S,H,W,4]`` -> (planar, packed)."""
     lib = _lib.load()

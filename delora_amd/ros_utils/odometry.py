@@ -16,7 +16,7 @@ import math
 import numpy as np
 import torch
 
-from .. import geometry
+from .. import _lib, geometry
 from ..models import model as model_module
 from ..models import model_parts
 
@@ -85,6 +85,31 @@ def filter_scans(scan):
     return scan[:, :, keep]
 
 
+def record_layout(dtype_or_step, offsets=None, filter=_lib.RECORDS_DROP_ZERO | _lib.RECORDS_MIN_RANGE, min_range=0.3):
+    """The ``_lib.RecordLayout`` of a message: a numpy structured dtype with fp32 fields ``x``, ``y``, ``z`` (what ``ros_numpy.numpify``
+    returns for a PointCloud2: its itemsize is the message's point_step), or ``(point_step, (off_x, off_y, off_z))`` in bytes.  The
+    default filter is the node's (odometry_publisher.py:95-97): exactly-zero coordinates and ranges within 0.3 m are dropped."""
+    if offsets is None:
+        dtype = np.dtype(dtype_or_step)
+        if dtype.fields is None or any(name not in dtype.fields for name in "xyz"):
+            raise ValueError(f"record_layout: {dtype} is not a structured dtype with fields x, y, z")
+        for name in "xyz":
+            if dtype.fields[name][0] != np.dtype("<f4"):
+                raise ValueError(f"record_layout: field {name} is {dtype.fields[name][0]}, only little-endian float32 is served")
+        dtype_or_step, offsets = dtype.itemsize, tuple(dtype.fields[name][1] for name in "xyz")
+    return geometry.record_layout(dtype_or_step, offsets, filter, min_range)
+
+
+def unpack_records(message, layout):
+    """``[1,3,N]`` fp32 from a message's raw records on the host (any point_step and offsets, unaligned ones included)."""
+    raw = np.ascontiguousarray(message).reshape(-1).view(np.uint8)
+    if raw.size % layout.point_step:
+        raise ValueError(f"{raw.size} bytes are not whole records of {layout.point_step} bytes")
+    raw = raw.reshape(-1, layout.point_step)
+    xyz = [np.ascontiguousarray(raw[:, o:o + 4]).view("<f4")[:, 0] for o in (layout.off_x, layout.off_y, layout.off_z)]
+    return np.stack(xyz, axis=0)[None].astype(np.float32, copy=False)
+
+
 def _project_pair_hip(previous, current, sensor):
     """Both scans through one launch of the HIP projection -> ``[2,4,H,W]`` (x, y, z, range)."""
     pts = torch.cat((previous[0, :3], current[0, :3]), dim=1).contiguous().float()
@@ -104,7 +129,10 @@ class ScanToScanOdometry(object):
     ``engine``: "torch" (default) runs the model's modules on the stacked pair; "native" drives ``dl_odometry_push`` (the torch-free
     C ABI of include/delora_hip.h, through ``deploy.native_infer.NativeOdometry``) with two ping-pong images -- the same kernels on the
     same operands, so the same numbers, for the configs that path serves: the 8-channel full-width network with two-MLP heads and no
-    ``normalization_scaling``; anything else raises ``ValueError`` at construction."""
+    ``normalization_scaling``; anything else raises ``ValueError`` at construction.
+
+    ``push_records`` takes a message as the driver delivers it (raw point records); on the native engine the node's filter runs inside
+    the library's projection (``dl_odometry_push_records``) and the host never touches the points."""
 
     def __init__(self, config, model=None, project_pair=None, engine="torch"):
         if engine not in ("torch", "native"):
@@ -191,3 +219,27 @@ class ScanToScanOdometry(object):
                 result.update(global_translation=gt, global_quaternion=gq, T_0_t=self.integrator.T_0_t[0].copy())
         self.point_cloud_t_1 = current * self.scaling_factor                    # undo the in-place scaling (:172)
         return result
+
+    @torch.no_grad()
+    def push_records(self, message, layout=None):
+        """``push`` for a message as the driver delivers it: a numpy structured array (``layout`` defaults to ``record_layout`` of its
+        dtype), a ``[N,C]`` fp32 array (a KITTI .bin file: x, y, z first) or raw bytes with an explicit ``layout``.  The node's filter
+        always applies.  Engine "native" hands the records to ``dl_odometry_push_records``: filter, projection and network in the
+        library, no host pass over the points.  Engine "torch", and any layout the library refuses (a 22-byte record), unpacks on the
+        host into ``[1,3,N]`` and goes through ``push`` -- the reference's route.  Returns what ``push`` returns."""
+        message = np.asarray(message)
+        if layout is None:
+            if message.dtype.fields is not None:
+                layout = record_layout(message.dtype)
+            elif message.dtype == np.float32 and message.ndim == 2 and message.shape[1] >= 3:
+                layout = record_layout(4 * message.shape[1], (0, 4, 8))
+            else:
+                raise ValueError("push_records: a layout is needed for anything but a structured array or [N,C>=3] float32")
+        layout = geometry.record_layout(layout.point_step, (layout.off_x, layout.off_y, layout.off_z),
+                                        _lib.RECORDS_DROP_ZERO | _lib.RECORDS_MIN_RANGE, 0.3)
+        if self.native is not None and message.flags.c_contiguous:
+            from ..deploy import native_infer
+            if native_infer.why_layout_unsupported(layout) is None:
+                out = self.native.push_records(message, layout)
+                return None if out is None else self._result(out[2], out[0])
+        return self.push(unpack_records(message, layout))

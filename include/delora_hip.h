@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), the narrow convolution family dl_tower_* (purely additive: the number stays), its strided / 1x1 / residual members for narrow pose networks dl_narrow_* (purely additive: the number stays),dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays), inference without Python: dl_pose_net_* / dl_odometry_* (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
+#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), the narrow convolution family dl_tower_* (purely additive: the number stays), its strided / 1x1 / residual members for narrow pose networks dl_narrow_* (purely additive: the number stays),dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays), inference without Python: dl_pose_net_* / dl_odometry_* (purely additive: the number stays), projection and streaming odometry from raw point records: dl_project_records / dl_odometry_push_records (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
 
 typedef void* dl_stream;
 
@@ -107,6 +107,44 @@ int dl_project(const float* pts, int64_t pts_cs, int64_t n_cols, const int32_t* 
                int32_t max_n, const dl_sensor* sensor, float* image4, float* aux, float* packed,
                float* packed_aux, int32_t* pix2pt, void* workspace, int32_t* kept, float* uvr,
                dl_stream stream);
+
+/*
+ * The same projection from RAW POINT RECORDS, with the reference node's filter applied inside the vote (additive: the ABI number
+ * stays).  A sensor driver delivers a scan as n records of point_step bytes with fp32 x, y, z at byte offsets -- a KITTI .bin file is
+ * point_step 16, offsets 0, 4, 8; a PointCloud2 message names its own -- and the reference's node (src/ros_utils/
+ * odometry_publisher.py:91-100) drops every point with an exactly zero coordinate or within 0.3 m on the host before it projects.
+ *   records  n_records records (device), 4-byte aligned; scan s owns records offs[s]..offs[s+1)
+ *   layout   passed by value semantics (read on the host during the call)
+ *   offs     [S+1] int32 CSR offsets in records (device); max_n >= the largest scan length (host value, sizes the grid only);
+ *            a record index outside [0, n_records) gives no load and no vote
+ *   image4 [S][4][H][W], packed [S][H][W][4] (may be NULL), pix2pt [S][H][W], kept [S] (may be NULL): as dl_project, pix2pt holding
+ *            the winner's RECORD index within its scan;  n_pass [S] out (may be NULL): records that took part
+ *   workspace dl_project_records_workspace_bytes(S,H,W) = S*H*W*8 rounded up to 16 bytes, 16-byte aligned: the key plane ONLY.
+ *            There are no staging records: resolve gathers x, y, z of the one winning record per occupied pixel from `records`
+ *            and takes the range from the winning key's upper word, the bits the vote computed.
+ * The contract, bit for bit (tests/records_ref.py is its plain restatement):
+ *   x, y, z are the fp32 words at the three offsets of record i; no other byte of a record influences anything;
+ *   a record takes part iff (!(filter & DL_RECORDS_DROP_ZERO) or (x != 0 and y != 0 and z != 0): -0.0 counts as zero, NaN does not)
+ *     and (!(filter & DL_RECORDS_MIN_RANGE) or range_np > min_range), range_np = sqrt((x*x + y*y) + z*z) with every operation
+ *     rounded to fp32 and NOTHING fused -- what numpy.linalg.norm(xyz, axis=0) computes, NOT dl_project's fused range: near 0.3 m
+ *     the two disagree about the threshold for ~1 % of the points within a few ulp of it.  A NaN comparison is false;
+ *   a record that takes part is projected exactly as dl_project projects a point (the fused range in the key, the image and the
+ *     packed image included), its index being the record index within its scan.
+ *   Hence image4, packed and kept equal dl_project on the host-filtered, compacted, transposed list, pix2pt equals its pix2pt mapped
+ *   through the list of surviving record indices, and n_pass is that list's length.
+ * Layouts served: point_step a multiple of 4 in 12..256; the three offsets multiples of 4, distinct, off + 4 <= point_step; records
+ * 4-byte aligned; min_range finite under DL_RECORDS_MIN_RANGE.  Any other layout is DL_ERR_UNSUPPORTED with a text naming the field
+ * (a 22-byte record has to be unpacked by the caller: no misaligned device loads).  A null pointer, an unknown filter bit, bad
+ * sizes or a misaligned workspace are DL_ERR_INVALID_ARGUMENT.  Every refusal happens before any launch.  16-byte records on a
+ * 16-byte aligned base are read with one 16-byte load per record, every other layout with three 4-byte loads at the record stride.
+ */
+#define DL_RECORDS_DROP_ZERO 1u   /* drop a record whose x, y or z is exactly zero (odometry_publisher.py:95) */
+#define DL_RECORDS_MIN_RANGE 2u   /* drop a record unless range_np > min_range (:96-97) */
+typedef struct { int32_t point_step, off_x, off_y, off_z; uint32_t filter; float min_range; } dl_record_layout;
+size_t dl_project_records_workspace_bytes(int32_t S, int32_t H, int32_t W);
+int dl_project_records(const void* records, int64_t n_records, const dl_record_layout* layout, const int32_t* offs, int32_t S, int32_t max_n,
+                       const dl_sensor* sensor, float* image4, float* packed, int32_t* pix2pt, void* workspace, int32_t* kept, int32_t* n_pass,
+                       dl_stream stream);
 
 /*
  * Per-pixel surface normals of S range images.
@@ -825,6 +863,12 @@ int dl_mean_hw_nhwc_f32(const float* x, int32_t N, int32_t P, int32_t C, float* 
  * aligned, H and W being the sensor's; every push needs 0 <= n_points <= max_points (the projection's staging records are the tail of
  * the workspace).  The reference's normalization_scaling rescales both clouds per pair and is not served: the previous image could
  * not be reused.
+ *
+ * dl_odometry_push_records is dl_odometry_push with the projection swapped for dl_project_records (S = 1): the new scan arrives as
+ * n_records raw records (device) with a dl_record_layout, filter included, and nothing has to be filtered, compacted or transposed
+ * first.  The same image_prev == NULL first-scan rule, the same offs [2] vector written on the stream, the same forward, the same
+ * refusals (plus the layout's, before any launch).  Its workspace is dl_odometry_workspace_bytes(net, sensor, 0, H, W) bytes for ANY
+ * n_records: the records path keeps no staging records, so nothing in the workspace grows with the scan.
  */
 #define DL_POSE_ACT_TANH 1
 #define DL_POSE_ACT_RELU 2
@@ -853,6 +897,9 @@ size_t dl_odometry_workspace_bytes(const dl_pose_net* net, const dl_sensor* sens
 int dl_odometry_push(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs,
                      int32_t n_points, int32_t* offs, const float* image_prev, float* image_cur, void* workspace, float* translation,
                      float* quaternion, float* T, dl_stream stream);
+int dl_odometry_push_records(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records, int32_t n_records,
+                             const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur, void* workspace,
+                             float* translation, float* quaternion, float* T, dl_stream stream);
 
 /*
  * What the convolution dispatch would launch (for tests and tools; host only, nothing is enqueued): runs the matching entry point's

@@ -3,7 +3,12 @@
 // as INTEGRATION.md section C describes for a C or C++ caller.  The counterpart of the reference's inference node (bin/run_rosnode.py)
 // without ROS.
 //
-//   odometry_demo <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...
+//   odometry_demo [--records <point_step> <off_x> <off_y> <off_z>] <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...
+//
+// With --records the scan files are raw point records as a sensor driver writes them (fp32 x, y, z at the three byte offsets of
+// point_step-byte records; a KITTI .bin file is --records 16 0 4 8): they are uploaded as they are and pushed through
+// dl_odometry_push_records with the reference node's filter (exactly-zero coordinates and ranges within 0.3 m are dropped inside
+// the projection) -- nothing is filtered, compacted or transposed on the host.
 //
 // One line per pair of consecutive scans:   <index> T <16 x 8 hex digits> pose <12 numbers>
 // T = the fp32 bit patterns of the row-major 4x4 transform (previous -> current), pose = the first three rows of the accumulated
@@ -148,7 +153,27 @@ static std::vector<char> read_file(const char* path) {
 }
 
 int main(int argc, char** argv) {
-  if (argc < 5) die("usage: odometry_demo <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...   (scans: float32 [3][N])");
+  // ---- the optional record layout
+  bool records = false;
+  dl_record_layout layout = {12, 0, 4, 8, DL_RECORDS_DROP_ZERO | DL_RECORDS_MIN_RANGE, 0.3f};
+  if (argc > 1 && !strcmp(argv[1], "--records")) {
+    if (argc < 6) die("--records needs <point_step> <off_x> <off_y> <off_z>");
+    int32_t* field[4] = {&layout.point_step, &layout.off_x, &layout.off_y, &layout.off_z};
+    for (int k = 0; k < 4; ++k) {
+      char* after = nullptr;
+      const long v = strtol(argv[2 + k], &after, 10);
+      if (after == argv[2 + k] || *after || v < -(1 << 20) || v > (1 << 20)) die(std::string("--records: not a number: ") + argv[2 + k]);
+      *field[k] = (int32_t)v;
+    }
+    if (layout.point_step < 1) die("--records: point_step must be positive");
+    records = true;
+    argc -= 5;
+    argv += 5;
+  }
+  if (argc < 5)
+    die("usage: odometry_demo [--records <point_step> <off_x> <off_y> <off_z>] <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...   (scans: "
+        "float32 [3][N], or raw records with --records)");
+  const size_t unit = records ? (size_t)layout.point_step : 12;        // bytes per point in a scan file
   // ---- the weight file
   const std::vector<char> blob = read_file(argv[1]);
   if (blob.size() < 16 || memcmp(blob.data(), "DLPOSNET", 8)) die("the weight file has a wrong magic");
@@ -220,15 +245,16 @@ int main(int argc, char** argv) {
   size_t max_points = 0;
   for (int i = 3; i < argc; ++i) {
     scans.push_back(read_file(argv[i]));
-    if (scans.back().size() % 12) die(std::string(argv[i]) + " is not a float32 [3][N] file");
-    if (scans.back().size() / 12 > ((size_t)1 << 30)) die(std::string(argv[i]) + " is too large");
-    if (scans.back().size() / 12 > max_points) max_points = scans.back().size() / 12;
+    if (scans.back().size() % unit) die(std::string(argv[i]) + (records ? " does not hold whole records" : " is not a float32 [3][N] file"));
+    if (scans.back().size() / unit > ((size_t)1 << 30)) die(std::string(argv[i]) + " is too large");
+    if (scans.back().size() / unit > max_points) max_points = scans.back().size() / unit;
   }
 
   // ---- buffers: all owned here, the library allocates nothing
   const size_t prepared_bytes = dl_pose_net_prepared_bytes(&net, 1, H, W);
   if (!prepared_bytes) die(std::string("dl_pose_net_prepared_bytes: ") + dl_last_error());
-  const size_t ws_bytes = dl_odometry_workspace_bytes(&net, &sensor, (int32_t)max_points, H, W);
+  // (the records path keeps no staging records: its workspace does not grow with the scan)
+  const size_t ws_bytes = dl_odometry_workspace_bytes(&net, &sensor, records ? 0 : (int32_t)max_points, H, W);
   if (!ws_bytes) die(std::string("dl_odometry_workspace_bytes: ") + dl_last_error());
   void *prepared = nullptr, *workspace = nullptr;
   float *images[2] = {nullptr, nullptr}, *d_pts = nullptr, *d_out = nullptr;
@@ -237,7 +263,7 @@ int main(int argc, char** argv) {
   HIP_OK(hipMalloc(&workspace, ws_bytes));
   HIP_OK(hipMalloc((void**)&images[0], (size_t)4 * H * W * 4));
   HIP_OK(hipMalloc((void**)&images[1], (size_t)4 * H * W * 4));
-  HIP_OK(hipMalloc((void**)&d_pts, max_points ? max_points * 12 : 256));
+  HIP_OK(hipMalloc((void**)&d_pts, max_points ? max_points * unit : 256));
   HIP_OK(hipMalloc((void**)&d_offs, 256));
   HIP_OK(hipMalloc((void**)&d_out, 256));                              // translation [3] | quaternion [4] | T [16] at floats 0, 4, 8
   hipStream_t stream;
@@ -249,11 +275,15 @@ int main(int argc, char** argv) {
   double pose[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
   int cur = 0;
   for (size_t i = 0; i < scans.size(); ++i) {
-    const size_t n = scans[i].size() / 12;
-    if (n) HIP_OK(hipMemcpyAsync(d_pts, scans[i].data(), n * 12, hipMemcpyHostToDevice, stream));
+    const size_t n = scans[i].size() / unit;
+    if (n) HIP_OK(hipMemcpyAsync(d_pts, scans[i].data(), n * unit, hipMemcpyHostToDevice, stream));
     if (i) cur = 1 - cur;                                            // the caller's swap of the two image buffers
-    DL_OK_OR_DIE(dl_odometry_push(&net, prepared, &sensor, d_pts, (int64_t)n, (int32_t)n, d_offs, i ? images[1 - cur] : nullptr, images[cur], workspace,
-                                  d_out, d_out + 4, d_out + 8, stream));
+    if (records)
+      DL_OK_OR_DIE(dl_odometry_push_records(&net, prepared, &sensor, d_pts, (int32_t)n, &layout, d_offs, i ? images[1 - cur] : nullptr, images[cur],
+                                            workspace, d_out, d_out + 4, d_out + 8, stream));
+    else
+      DL_OK_OR_DIE(dl_odometry_push(&net, prepared, &sensor, d_pts, (int64_t)n, (int32_t)n, d_offs, i ? images[1 - cur] : nullptr, images[cur], workspace,
+                                    d_out, d_out + 4, d_out + 8, stream));
     float T[16];
     if (i) HIP_OK(hipMemcpyAsync(T, d_out + 8, sizeof(T), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));                            // (also: the scan buffer is free for the next copy)
