@@ -688,7 +688,10 @@ int dl_conv2d_wgrad_batch_nhwc_h(const dl_wgrad_h_layer* layers, int32_t n, void
  *                           greater value wins, NaN propagates; the column left of column 0 is column W-1)
  *   dl_pool3x3s12_nhwc_bwd: g [N][H][W/2][C], a, win -> g_conv [N][H][W][C] = act'(a) * (sum of g over the windows that
  *                           selected the element); act: 0 none, 1 tanh (1 - a^2), 2 relu (a > 0)
- *   W even, C % 4 == 0.
+ *   W even, C % 4 == 0.  The forward takes any a: a window of -inf gives -inf at its first in-range position (0, or 3 in row 0),
+ *   the LAST NaN of a window wins, of equal zeros the first keeps its sign.  The backward (and dl_stem_wgrad_f32 below) needs a
+ *   FINITE a: relu' is evaluated as "0 where a <= 0, else 1", which agrees with a > 0 on every finite value and on +-0 but lets
+ *   the gradient through at a NaN.  g may hold anything: a gradient reaches only the element its window selected.
  */
 int dl_pool3x3s12_nhwc_fwd(const float* a, int32_t N, int32_t H, int32_t W, int32_t C, float* y, int8_t* win, dl_stream stream);
 int dl_pool3x3s12_nhwc_bwd(const float* g, const float* a, const int8_t* win, int32_t N, int32_t H, int32_t W, int32_t C,
