@@ -41,6 +41,8 @@ SIGNATURES = {
     "dl_last_error": (ctypes.c_char_p, []),
     "dl_project_workspace_bytes": (_sz, [_i32, _i32, _i32, _i64, _i32]),
     "dl_project": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dl_project_rotated": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dl_rotations_from_draws": (_i32, [_vp, _i32, _i32, _f32, _vp, _vp]),
     "dl_project_records_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dl_project_records": (_i32, [_vp, _i64, _RP, _vp, _i32, _i32, _SP, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dl_reproject_workspace_bytes": (_sz, [_i32, _i32, _i32]),

@@ -136,6 +136,116 @@ __global__ __launch_bounds__(DL_BLOCK) void k_project_resolve(
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Rotation augmentation inside the vote (dl_project_rotated): scan s is replaced by R_s p (and R_s n for stored normals) where x, y,
+// z are in registers anyway -- no extra pass over the points and no write to the caller's buffer.  One row of a rotated point is
+// (r0*x + r1*y) + r2*z, every operation rounded to fp32, nothing contracted (the pragma holds under any -ffp-contract setting), so
+// that a numpy fp32 expression reproduces it bit for bit.
+__device__ __forceinline__ float rot_row(float r0, float r1, float r2, float x, float y, float z) {
+#pragma clang fp contract(off)
+  const float a = r0 * x;
+  const float b = r1 * y;
+  const float c = r2 * z;
+  const float ab = a + b;
+  return ab + c;
+}
+
+// The vote of k_project_scatter (kept there word for word: its code is not touched) on the rotated point.  rot [S][9] row-major; a
+// scan whose nine words are the bit pattern of the identity is NOT multiplied (x * 1 + y * 0 would turn -0.0 into +0.0 and inf into
+// NaN): the decision depends on the scan alone, so it is uniform per workgroup.  Everything downstream -- range, coordinates, uvr,
+// the staging records k_project_resolve gathers from -- sees the rotated values only.
+__global__ __launch_bounds__(DL_BLOCK) void k_project_scatter_rot(
+    const float* __restrict__ pts, int64_t cs, const int32_t* __restrict__ offs, int S, int C, int G, SensorK sen,
+    unsigned long long* __restrict__ keys, float4* __restrict__ stage0, float4* __restrict__ stage1, float* __restrict__ uvr, int64_t n_cols,
+    const float* __restrict__ rot) {
+  int s, chunk;
+  if (!project_block(S, G, s, chunk)) return;
+  const int n0 = offs[s];
+  const int n = offs[s + 1] - n0;
+  float R[9];
+  bool rotate = false;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    R[k] = rot[(size_t)s * 9 + k];
+    rotate |= __float_as_uint(R[k]) != ((k & 3) == 0 ? 0x3f800000u : 0u);
+  }
+  unsigned long long* kp = keys + (size_t)s * sen.HW;
+  const int stride = (G < 0 ? -G : G) * DL_BLOCK;
+  for (int i = chunk * DL_BLOCK + threadIdx.x; i < n; i += stride) {
+    const int64_t g = (int64_t)n0 + i;
+    float x = pts[g], y = pts[cs + g], z = pts[2 * cs + g];
+    if (rotate) {
+      const float px = x, py = y, pz = z;
+      x = rot_row(R[0], R[1], R[2], px, py, pz);
+      y = rot_row(R[3], R[4], R[5], px, py, pz);
+      z = rot_row(R[6], R[7], R[8], px, py, pz);
+    }
+    const float r = norm3f(x, y, z);
+    float u = coord_u_fast(x, y, sen);
+    float v = coord_v_fast(x, y, z, sen);
+    if (uvr || near_rounding_boundary(u, sen.tol_u) || near_rounding_boundary(v, sen.tol_v)) {
+      u = coord_u(x, y, sen);
+      v = coord_v(x, y, z, sen);
+    }
+    if (uvr) { uvr[g] = u; uvr[cs + g] = v; uvr[2 * cs + g] = r; }
+    if (g >= n_cols) continue;                  // offsets that disagree with the sized workspace: no store, no vote
+    stage0[g] = make_float4(x, y, z, r);
+    if (stage1) {
+      float a = pts[3 * cs + g], b = C > 4 ? pts[4 * cs + g] : 0.f, c = C > 5 ? pts[5 * cs + g] : 0.f;
+      if (rotate && C > 5) {                    // channels 3..5 are a vector (the stored normals) only when all three are there
+        const float pa = a, pb = b, pc = c;
+        a = rot_row(R[0], R[1], R[2], pa, pb, pc);
+        b = rot_row(R[3], R[4], R[5], pa, pb, pc);
+        c = rot_row(R[6], R[7], R[8], pa, pb, pc);
+      }
+      stage1[g] = make_float4(a, b, c, 0.f);
+    }
+    const float ru = rintf(u), rv = rintf(v);   // torch.round: half to even
+    if (ru <= sen.wm1f && ru >= 0.0f && rv <= sen.hm1f && rv >= 0.0f) {   // projection.py:74-75
+      const unsigned long long key = ((unsigned long long)__float_as_uint(r) << 32) | (unsigned int)i;
+      atomicMin(&kp[(int)rv * sen.W + (int)ru], key);
+    }
+  }
+}
+
+// Rotations of one training step from uniform draws (the reference's dead branch, src/deploy/deployer.py:205-214, per sample):
+// row 2b is the exact identity (scan 1 is never rotated), row 2b+1 is Rodrigues' matrix of the unit axis d and the angle
+// a = (u3 - 0.5) * magnitude: R = cos(a) I + sin(a) [d]x + (1 - cos(a)) d d^T.  The axis is (0, 0, 1) with only_yaw, else the three
+// draws normalised (all in [0, 1): the reference's positive-octant quirk).  a == 0, or three zero draws (no axis), give the exact
+// identity; only_yaw writes row and column 2 as exact 0 / 1.
+__global__ void k_rotations_from_draws(const float* __restrict__ draws, int B, int only_yaw, float magnitude, float* __restrict__ rot) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float* I = rot + (size_t)b * 18;
+  float* R = I + 9;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) I[k] = (k & 3) == 0 ? 1.f : 0.f;
+  const float a = (draws[4 * b + 3] - 0.5f) * magnitude;
+  float dx = 0.f, dy = 0.f, dz = 1.f;
+  bool none = a == 0.f;
+  if (!only_yaw) {
+    dx = draws[4 * b]; dy = draws[4 * b + 1]; dz = draws[4 * b + 2];
+    const float len = norm3f(dx, dy, dz);
+    none |= !(len > 0.f);
+    dx /= len; dy /= len; dz /= len;
+  }
+  if (none) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = (k & 3) == 0 ? 1.f : 0.f;
+    return;
+  }
+  const float sn = sinf(a), cn = cosf(a), t = 1.f - cn;
+  if (only_yaw) {
+    R[0] = cn; R[1] = -sn; R[2] = 0.f;
+    R[3] = sn; R[4] = cn; R[5] = 0.f;
+    R[6] = 0.f; R[7] = 0.f; R[8] = 1.f;
+    return;
+  }
+  R[0] = cn + t * dx * dx; R[1] = t * dx * dy - sn * dz; R[2] = t * dx * dz + sn * dy;
+  R[3] = t * dx * dy + sn * dz; R[4] = cn + t * dy * dy; R[5] = t * dy * dz - sn * dx;
+  R[6] = t * dx * dz - sn * dy; R[7] = t * dy * dz + sn * dx; R[8] = cn + t * dz * dz;
+}
+
 // (advisor, round 5) the staging records behind the key plane are read and written as float4: the plane's size is rounded up to 16 bytes
 // (S*H*W odd would leave them 8-byte aligned); the vote's staging stores are guarded by the record count the workspace was sized for
 static inline size_t project_keys_bytes(int32_t S, int32_t H, int32_t W) { return (((size_t)S * H * W * sizeof(uint64_t)) + 15) & ~(size_t)15; }
@@ -145,19 +255,20 @@ extern "C" size_t dl_project_workspace_bytes(int32_t S, int32_t H, int32_t W, in
   return project_keys_bytes(S, H, W) + (size_t)n_cols * 16 * (C > 3 ? 2 : 1);
 }
 
-extern "C" int dl_project(const float* pts, int64_t pts_cs, int64_t n_cols, const int32_t* offs, int32_t S, int32_t C,
-                          int32_t max_n, const dl_sensor* sensor, float* image4, float* aux, float* packed,
-                          float* packed_aux, int32_t* pix2pt, void* workspace, int32_t* kept, float* uvr,
-                          dl_stream stream) {
+// dl_project (rot == NULL: the launches it always made) and dl_project_rotated behind one set of refusals
+static int project_impl(const char* who, const float* pts, int64_t pts_cs, int64_t n_cols, const int32_t* offs, int32_t S, int32_t C,
+                        int32_t max_n, const dl_sensor* sensor, float* image4, float* aux, float* packed,
+                        float* packed_aux, int32_t* pix2pt, void* workspace, int32_t* kept, float* uvr, const float* rot,
+                        dl_stream stream) {
   if ((!pts && max_n > 0) || !offs || !sensor || !image4 || !pix2pt || !workspace)
-    return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_project: null pointer argument");
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument", who);
   if (S <= 0 || C < 3 || sensor->H < 2 || sensor->W < 2 || max_n < 0 || n_cols < 0 || n_cols > pts_cs)
-    return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_project: bad sizes S=%d C=%d H=%d W=%d max_n=%d n_cols=%lld pts_cs=%lld", S, C,
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad sizes S=%d C=%d H=%d W=%d max_n=%d n_cols=%lld pts_cs=%lld", who, S, C,
                    sensor->H, sensor->W, max_n, (long long)n_cols, (long long)pts_cs);
-  if (C > 3 && !aux) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_project: C=%d needs an aux image", C);
-  if (packed_aux && C < 6) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_project: packed_aux needs C >= 6 (got %d)", C);
+  if (C > 3 && !aux) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: C=%d needs an aux image", who, C);
+  if (packed_aux && C < 6) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: packed_aux needs C >= 6 (got %d)", who, C);
   // the staging records behind the key plane are read and written as float4
-  if ((uintptr_t)workspace & 15) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_project: workspace must be 16-byte aligned");
+  if ((uintptr_t)workspace & 15) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
   hipStream_t st = (hipStream_t)stream;
   const SensorK sen = make_sensor(sensor);
   // workspace = key plane [S][H*W] uint64 | staging records [n_cols] float4 (x,y,z,range) | [n_cols] float4 (channels 3..5) if C > 3
@@ -171,14 +282,45 @@ extern "C" int dl_project(const float* pts, int64_t pts_cs, int64_t n_cols, cons
   if (max_n > 0) {
     int G = (max_n + DL_BLOCK - 1) / DL_BLOCK;
     if (G > 1024) G = 1024;
-    hipLaunchKernelGGL(k_project_scatter, dim3(project_grid(S, G)), dim3(DL_BLOCK), 0, st, pts, pts_cs, offs, S, C, project_garg(S, G),
-                       sen, keys, stage0, stage1, uvr, n_cols);
+    if (rot)
+      hipLaunchKernelGGL(k_project_scatter_rot, dim3(project_grid(S, G)), dim3(DL_BLOCK), 0, st, pts, pts_cs, offs, S, C, project_garg(S, G),
+                         sen, keys, stage0, stage1, uvr, n_cols, rot);
+    else
+      hipLaunchKernelGGL(k_project_scatter, dim3(project_grid(S, G)), dim3(DL_BLOCK), 0, st, pts, pts_cs, offs, S, C, project_garg(S, G),
+                         sen, keys, stage0, stage1, uvr, n_cols);
   }
   const int G = (sen.HW + DL_BLOCK - 1) / DL_BLOCK;
   hipLaunchKernelGGL(k_project_resolve, dim3(project_grid(S, G)), dim3(DL_BLOCK), 0, st, pts, pts_cs, offs, S, C, project_garg(S, G), sen,
                      (const unsigned long long*)keys, (const float4*)stage0, (const float4*)stage1, image4, aux,
                      (float4*)packed, (float4*)packed_aux, pix2pt, kept);
-  return dl_check_launch("dl_project");
+  return dl_check_launch(who);
+}
+
+extern "C" int dl_project(const float* pts, int64_t pts_cs, int64_t n_cols, const int32_t* offs, int32_t S, int32_t C,
+                          int32_t max_n, const dl_sensor* sensor, float* image4, float* aux, float* packed,
+                          float* packed_aux, int32_t* pix2pt, void* workspace, int32_t* kept, float* uvr,
+                          dl_stream stream) {
+  return project_impl("dl_project", pts, pts_cs, n_cols, offs, S, C, max_n, sensor, image4, aux, packed, packed_aux, pix2pt, workspace, kept,
+                      uvr, nullptr, stream);
+}
+
+extern "C" int dl_project_rotated(const float* pts, int64_t pts_cs, int64_t n_cols, const int32_t* offs, int32_t S, int32_t C,
+                                  int32_t max_n, const dl_sensor* sensor, float* image4, float* aux, float* packed,
+                                  float* packed_aux, int32_t* pix2pt, void* workspace, int32_t* kept, float* uvr,
+                                  const float* rot, dl_stream stream) {
+  if ((uintptr_t)rot & 3) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_project_rotated: rot must be 4-byte aligned");
+  return project_impl("dl_project_rotated", pts, pts_cs, n_cols, offs, S, C, max_n, sensor, image4, aux, packed, packed_aux, pix2pt,
+                      workspace, kept, uvr, rot, stream);
+}
+
+extern "C" int dl_rotations_from_draws(const float* draws, int32_t B, int32_t only_yaw, float magnitude_rad, float* rot, dl_stream stream) {
+  if (!draws || !rot) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_rotations_from_draws: null pointer argument");
+  if (B <= 0 || !(fabsf(magnitude_rad) <= 3.402823466e38f))
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_rotations_from_draws: bad sizes B=%d magnitude_rad=%g", B, (double)magnitude_rad);
+  if (((uintptr_t)draws | (uintptr_t)rot) & 3) return dl_fail(DL_ERR_INVALID_ARGUMENT, "dl_rotations_from_draws: draws and rot must be 4-byte aligned");
+  hipLaunchKernelGGL(k_rotations_from_draws, dim3((B + DL_WAVE - 1) / DL_WAVE), dim3(DL_WAVE), 0, (hipStream_t)stream, draws, B, only_yaw ? 1 : 0,
+                     magnitude_rad, rot);
+  return dl_check_launch("dl_rotations_from_draws");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -327,13 +327,13 @@ class PackedFeed:
 
 def packed_feed_applicable(dataset, config, device):
     """Whether the training set can go through ``PackedFeed``: a CUDA device, the reference's dataset (on disk or in RAM) over ONE
-    dataset block (one sensor per batch), no per-sample host preprocessing (augmentation / range normalisation work on the sample
-    dicts).  Any worker count, 0 included (the consumer then decodes in-process): the DataLoader path re-pins every tensor of every
+    dataset block (one sensor per batch), no per-sample host preprocessing (range normalisation works on the sample dicts; the
+    rotation augmentation does not: it happens inside the projection kernel, for a packed batch as for a list).  Any worker count, 0 included (the consumer then decodes in-process): the DataLoader path re-pins every tensor of every
     batch and costs the host tens of milliseconds per step -- it remains for what the packed layout cannot express."""
     from .dataset import PreprocessedPointCloudDataset
     return (isinstance(dataset, PreprocessedPointCloudDataset) and len(config["datasets"]) == 1
             and int(config.get("num_dataloader_workers", 0)) >= 0 and bool(config.get("packed_feed", True))
-            and not config.get("normalization_scaling") and not config.get("random_point_cloud_rotations")
+            and not config.get("normalization_scaling")
             and getattr(device, "type", str(device)) == "cuda")
 
 

@@ -8,6 +8,7 @@ replaced by batched HIP launches (deploy/step_geometry.py) and nothing synchroni
 A logged step (``log_images_bool=True``) additionally fills the reference's six ``log_*`` images (deployer.py:61-66,73-89) through one
 re-projection launch of the backend (``step_images``); ``log_image`` draws them (utility/plotting.py).
 """
+import math
 import os
 
 import torch
@@ -79,9 +80,26 @@ class Deployer(object):
                 + transformation_matrix[:, :3, 3].view(-1, 3, 1))
 
     def augment_input(self, preprocessed_data):
-        if self.config["random_point_cloud_rotations"]:
-            raise Exception("Needs to be verified for larger batches")   # the reference refuses too (deployer.py:203-204)
+        """Kept for the reference's call order (deployer.py:201-220); the sample dict passes through unchanged.  The reference raises here
+        when ``random_point_cloud_rotations`` is set (:203-204); the branch behind that raise (:205-218) is what ``step_rotations`` and
+        the projection kernel implement for whole batches -- no per-dict torch route, so lists of dicts and packed batches take the same
+        kernel path and give the same bits, and cached scans (``store_dataset_in_RAM``, feed slots) are never rewritten."""
         return preprocessed_data
+
+    def step_rotations(self, B):
+        """(draws [B,4], rot [2B,9]) of one augmented training step, or (None, None): only a training step with
+        ``random_point_cloud_rotations`` draws, and it draws ONCE -- ``torch.rand((B, 4))`` from the device's default generator, so
+        ``torch.manual_seed`` reproduces a run (under DDP every rank draws from its own generator: seed the ranks differently, or all of
+        them rotate alike).  Per sample: the axis is (0, 0, 1) with ``random_rotations_only_yaw``, else draws 0..2 normalised (all in
+        [0, 1): the reference's positive-octant quirk, deployer.py:209-210, kept); the angle is (draw 3 - 0.5) *
+        ``magnitude_random_rot`` degrees (:211-213).  Row 2b of ``rot`` is the identity (scan 1 is untouched), row 2b+1 rotates scan 2
+        and its stored normals."""
+        if not (self.training_bool and self.config["random_point_cloud_rotations"]):
+            return None, None
+        draws = torch.rand((B, 4), device=self.device)
+        rot = geometry.rotations_from_draws(draws, bool(self.config["random_rotations_only_yaw"]),
+                                            math.radians(float(self.config["magnitude_random_rot"])))
+        return draws, rot
 
     def normalize_input(self, preprocessed_data):
         """Optional range normalisation (deployer.py:222-235): both scans divided by the mean of their mean ranges."""
@@ -145,14 +163,19 @@ class Deployer(object):
                 a += v
 
     def step(self, preprocessed_dicts, epoch_losses=None, log_images_bool=False):
+        """One step over a batch (a list of sample dicts, or a ``PackedBatch``).  Returns ``(epoch_losses, T [B,4,4])``, or ``T`` alone
+        with ``inference_only``.  ``T`` maps scan 2 AS THE NETWORK SAW IT onto scan 1: in a training step with
+        ``random_point_cloud_rotations`` that is the ROTATED scan 2 (``R p``; the matrices of the step are
+        ``last_step["rotations"]``, rows 2b+1), not the stored one.  Evaluation steps, the Tester and the inference paths never
+        augment."""
         cfg = self.config
         packed = preprocessed_dicts if isinstance(preprocessed_dicts, step_geometry.PackedBatch) else None
         B = len(preprocessed_dicts)
         if packed is not None:
             # a batch that already lies concatenated in static device buffers (deploy/graph_step.py): one sensor, no per-sample
             # host-side preprocessing
-            if (self.training_bool and cfg["random_point_cloud_rotations"]) or cfg["normalization_scaling"]:
-                raise ValueError("a PackedBatch cannot be augmented or range-normalised (config: random_point_cloud_rotations / normalization_scaling)")
+            if cfg["normalization_scaling"]:
+                raise ValueError("a PackedBatch cannot be range-normalised (config: normalization_scaling)")
             preprocessed_dicts = [{"dataset": packed.dataset}] * B
         if B != self.batch_size:
             # the reference indexes batch_size transforms against the list and fails on a short last batch
@@ -172,6 +195,9 @@ class Deployer(object):
         groups = {}
         for i, d in enumerate(preprocessed_dicts):
             groups.setdefault(self.img_projection.sensor(d["dataset"]).key(), []).append(i)
+        # rotation augmentation (training only): one draw per step, the matrices built on the device, the rotation applied inside the
+        # projection's vote -- for a list of dicts and for a PackedBatch alike
+        draws, rot = self.step_rotations(B)
         flags = geometry.loss_flags(cfg)
         T_rows, term_rows, count_rows, vis_rows = [None] * B, [None] * B, [None] * B, [None] * B
         # a logged step keeps (references to) what the figure is drawn from: the group of sample 0 and the group of the last sample
@@ -181,8 +207,11 @@ class Deployer(object):
         for idx in groups.values():
             dataset = preprocessed_dicts[idx[0]]["dataset"]
             sensor = self.img_projection.sensor(dataset)
+            extra = {}
+            if rot is not None:         # a mixed-sensor batch: the rows of this group's samples, in the group's order
+                extra["rotations"] = rot if len(groups) == 1 else torch.cat([rot[2 * i:2 * i + 2] for i in idx], dim=0)
             prepared = self.geo.prepare(packed if packed is not None else [preprocessed_dicts[i] for i in idx], sensor,
-                                        self._normal_params(dataset))
+                                        self._normal_params(dataset), **extra)
             translations, rotation_representation = self._run_model(prepared["stacked"])
             T_g = self.geometry_handler.get_transformation_matrix_quaternion(
                 translation=translations, quaternion=rotation_representation, device=self.device)
@@ -252,7 +281,9 @@ class Deployer(object):
             self._accumulate(epoch_losses, keys, vals)
         if want_images:
             self._fill_log_images(image_first, image_last)
-        self.last_step = {"loss_terms": terms.detach(), "pair_counts": counts, "losses": {k: v.detach() for k, v in losses.items()}}
+        # rotation_draws [B,4] / rotations [2B,9]: what this step's augmentation drew and applied (None when it did not augment)
+        self.last_step = {"loss_terms": terms.detach(), "pair_counts": counts, "losses": {k: v.detach() for k, v in losses.items()},
+                          "rotation_draws": draws, "rotations": rot}
         return epoch_losses, computed_transformations
 
     # ------------------------------------------------------------------------------------------------ the logged figure

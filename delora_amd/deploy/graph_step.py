@@ -59,7 +59,7 @@ class GraphedStep:
                            if dev.type == "cuda" and torch.cuda.is_available() else None)
         self._offs_events = [None] * 4
         self._offs_next = 0
-        # a PackedBatch cannot be augmented or rescaled (Deployer.step rejects it) and one capture serves one sensor and one rank:
+        # a PackedBatch cannot be rescaled (Deployer.step rejects it), an augmented step stays eager, and one capture serves one sensor and one rank:
         # when a requirement does not hold every call runs the eager step on the caller's own list of dicts
         self.eligible = GraphedStep.config_eligible(trainer) and len(datasets) == 1 and self.B == trainer.batch_size
         if not self.eligible:
@@ -174,8 +174,8 @@ class GraphedStep:
     @staticmethod
     def config_eligible(trainer):
         """Whether this trainer's configuration can run as a captured step at all (the batch-dependent requirements -- one sensor,
-        the configured batch size -- are checked per batch): one rank (DDP's bucketed all-reduce is left eager), no augmentation or
-        range normalisation (they work on the sample dicts), no float16 loss scaling (its skipped steps are host decisions)."""
+        the configured batch size -- are checked per batch): one rank (DDP's bucketed all-reduce is left eager), no range normalisation
+        (it works on the sample dicts), no rotation augmentation (a step that draws stays eager), no float16 loss scaling (its skipped steps are host decisions)."""
         cfg = trainer.config
         return not (trainer.world_size != 1 or cfg["normalization_scaling"] or cfg["random_point_cloud_rotations"]
                     or getattr(trainer, "grad_scaler", None) is not None or cfg.get("use_jit"))

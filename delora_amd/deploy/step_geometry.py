@@ -51,14 +51,17 @@ class HipStepGeometry:
             self._offsets[key] = t
         return t[0]
 
-    def prepare(self, samples, sensor, normal_params):
-        """samples: list of dicts with ``scan_1``/``scan_2`` ``[1,3,N]`` on the GPU and optional ``normal_list_*``.
+    def prepare(self, samples, sensor, normal_params, rotations=None):
+        """samples: list of dicts with ``scan_1``/``scan_2`` ``[1,3,N]`` on the GPU and optional ``normal_list_*``, or a ``PackedBatch``.
+        ``rotations``: None or ``[2B,9]`` fp32 on the device, one row per scan in the order b0.scan_1, b0.scan_2, b1.scan_1 ... (the
+        augmentation of a training step): applied inside the projection to points and stored normals alike, the inputs stay untouched;
+        online normals are estimated from the rotated image.
         Returns dict(stacked [B,8,H,W] network input, images [B,2,4,H,W] view, normals [B,2,3,H,W], their packed twins
         packed / normals_packed [B,2,H,W,4], pix2pt [B,2,H,W])."""
         B = len(samples)
         if isinstance(samples, PackedBatch):
             with_lists = samples.with_lists
-            out = geometry.project(samples.pts, samples.offs, samples.max_points, sensor, want_kept=False)
+            out = geometry.project(samples.pts, samples.offs, samples.max_points, sensor, want_kept=False, rotations=rotations)
         else:
             with_lists = samples[0].get("normal_list_1") is not None
             chunks, lengths = [], []
@@ -71,7 +74,7 @@ class HipStepGeometry:
                     lengths.append(scan.shape[1])
             pts = torch.cat(chunks, dim=1).contiguous().float()
             offs = self._offsets_for(lengths, pts.device)
-            out = geometry.project(pts, offs, max(lengths), sensor, want_kept=False)
+            out = geometry.project(pts, offs, max(lengths), sensor, want_kept=False, rotations=rotations)
         image4 = out["image4"]
         H, W = sensor.H, sensor.W
         if with_lists:

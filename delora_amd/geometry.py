@@ -58,8 +58,10 @@ def _planar(t, channels):
     return t, t.stride(0)
 
 
-def project(points, offsets, max_points, sensor, want_uv=False, want_kept=True, want_packed=True):
+def project(points, offsets, max_points, sensor, want_uv=False, want_kept=True, want_packed=True, rotations=None):
     """Range images of S scans.  points ``[C,sumN]`` fp32 (rows 0..2 = xyz), offsets ``[S+1]`` int32 (device).
+    ``rotations``: None, or ``[S,9]`` / ``[S,3,3]`` fp32 on the device -- scan s is projected as R_s p (stored normals as R_s n) inside
+    the vote (``dl_project_rotated``); an identity row leaves its scan bit-identical, ``points`` is never written.
     Returns dict(image4 [S,4,H,W], aux [S,C-3,H,W]|None, packed [S,H,W,4]|None, packed_aux [S,H,W,4]|None (C >= 6: the
     stored normals), pix2pt [S,H,W] int32, kept [S] int32|None, uv [3,sumN]|None = u, v and range of every point)."""
     lib = _lib.load()
@@ -81,11 +83,34 @@ def project(points, offsets, max_points, sensor, want_uv=False, want_kept=True, 
     uv = torch.empty((3, points.shape[1]), dtype=torch.float32, device=dev) if want_uv else None
     if uv is not None and points.stride(0) != uv.stride(0):
         raise ValueError("want_uv needs a dense points buffer")
-    _lib.check(lib.dl_project(_ptr(points), points.stride(0), n_cols, _ptr(offsets), S, C, int(max_points),
-                              ctypes.byref(sensor.struct), _ptr(image4), _ptr(aux), _ptr(packed), _ptr(packed_aux),
-                              _ptr(pix2pt), _ptr(ws), _ptr(kept), _ptr(uv), _stream()), "dl_project")
+    if rotations is None:
+        _lib.check(lib.dl_project(_ptr(points), points.stride(0), n_cols, _ptr(offsets), S, C, int(max_points),
+                                  ctypes.byref(sensor.struct), _ptr(image4), _ptr(aux), _ptr(packed), _ptr(packed_aux),
+                                  _ptr(pix2pt), _ptr(ws), _ptr(kept), _ptr(uv), _stream()), "dl_project")
+    else:
+        _require_cuda(rotations)
+        if rotations.dtype != torch.float32 or rotations.numel() != 9 * S or not rotations.is_contiguous():
+            raise ValueError(f"rotations must be contiguous fp32 [S,9] with S = {S}, got {tuple(rotations.shape)}")
+        _lib.check(lib.dl_project_rotated(_ptr(points), points.stride(0), n_cols, _ptr(offsets), S, C, int(max_points),
+                                          ctypes.byref(sensor.struct), _ptr(image4), _ptr(aux), _ptr(packed), _ptr(packed_aux),
+                                          _ptr(pix2pt), _ptr(ws), _ptr(kept), _ptr(uv), _ptr(rotations), _stream()), "dl_project_rotated")
     return {"image4": image4, "aux": aux, "packed": packed, "packed_aux": packed_aux, "pix2pt": pix2pt, "kept": kept,
             "uv": uv}
+
+
+def rotations_from_draws(draws, only_yaw, magnitude_rad):
+    """The rotations of one augmented training step (``dl_rotations_from_draws``): draws ``[B,4]`` fp32 uniform in [0, 1) on the device
+    (0..2 the direction, 3 the angle) -> ``[2B,9]`` fp32: row 2b the exact identity (scan 1), row 2b+1 Rodrigues' matrix of the axis
+    ((0, 0, 1) when ``only_yaw``, else the normalised draws) and the angle (u - 0.5) * ``magnitude_rad``.  One launch, no host sync."""
+    lib = _lib.load()
+    _require_cuda(draws)
+    if draws.dtype != torch.float32 or draws.dim() != 2 or draws.shape[1] != 4 or not draws.is_contiguous():
+        raise ValueError("draws must be contiguous fp32 [B,4]")
+    B = draws.shape[0]
+    rot = torch.empty((2 * B, 9), dtype=torch.float32, device=draws.device)
+    _lib.check(lib.dl_rotations_from_draws(_ptr(draws), B, 1 if only_yaw else 0, float(magnitude_rad), _ptr(rot), _stream()),
+               "dl_rotations_from_draws")
+    return rot
 
 
 def record_layout(point_step, offsets, filter=0, min_range=0.0):

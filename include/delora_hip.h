@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), the narrow convolution family dl_tower_* (purely additive: the number stays), its strided / 1x1 / residual members for narrow pose networks dl_narrow_* (purely additive: the number stays),dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays), inference without Python: dl_pose_net_* / dl_odometry_* (purely additive: the number stays), projection and streaming odometry from raw point records: dl_project_records / dl_odometry_push_records (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
+#define DL_ABI_VERSION 10   /* 10: dl_conv_plan_describe (additive), the narrow convolution family dl_tower_* (purely additive: the number stays), its strided / 1x1 / residual members for narrow pose networks dl_narrow_* (purely additive: the number stays),dl_reproject / dl_reproject_workspace_bytes (purely additive: the number stays), inference without Python: dl_pose_net_* / dl_odometry_* (purely additive: the number stays), projection and streaming odometry from raw point records: dl_project_records / dl_odometry_push_records (purely additive: the number stays), rotation augmentation inside the projection: dl_project_rotated / dl_rotations_from_draws (purely additive: the number stays); 9: exact tree search between free-form point lists (dl_nn_list_*; additive); 8: dropout on the HIP path (dl_dropout_scale_f32, dl_stem_input_nhwc_drop_f32, dl_channel_scale_*_nhwc_t, dl_heads_*_drop; additive); 7: the Winograd-domain weights are an opaque operand (blocked LDS-image layout); 6: dl_project takes n_cols and ONE workspace (key plane + staging records of the vote), dl_wino_conv3x3_nhwc_f32 an optional split-K workspace; 5: batched weight gradients (dl_conv2d_wgrad_batch_*); 4: free image sizes in the convolution family (the strided input gradients take the INPUT image size and a seam workspace); 3: half-precision convolutions, launch profiler */
 
 typedef void* dl_stream;
 
@@ -107,6 +107,38 @@ int dl_project(const float* pts, int64_t pts_cs, int64_t n_cols, const int32_t* 
                int32_t max_n, const dl_sensor* sensor, float* image4, float* aux, float* packed,
                float* packed_aux, int32_t* pix2pt, void* workspace, int32_t* kept, float* uvr,
                dl_stream stream);
+
+/*
+ * dl_project with a rotation per scan applied INSIDE the vote (additive: the ABI number stays) -- the training-time augmentation
+ * `random_point_cloud_rotations` (src/deploy/deployer.py:205-218, dead in the reference behind its raise at :203-204) without a
+ * pass of its own and without writing the caller's point buffer.  Every argument of dl_project, plus
+ *   rot      [S][9]        fp32 row-major 3x3 matrices (device), or NULL: exactly dl_project.
+ * The contract, bit for bit (tests/rotate_ref.py is its plain restatement):
+ *   a scan whose nine words are the bit pattern of the identity (1.0f on the diagonal, +0.0f elsewhere) is NOT multiplied: every
+ *     output of that scan is dl_project's, -0.0, inf and NaN coordinates included;
+ *   any other scan is projected as dl_project projects the points p' = R p, one coordinate being (r0*x + r1*y) + r2*z with every
+ *     operation rounded to fp32 and nothing fused; image4, packed, uvr and the winner follow from p' alone (pix2pt still indexes
+ *     the input columns);
+ *   with C >= 6 channels 3..5 (the stored normals) are rotated by the same matrix in the same arithmetic; with C = 4 or 5 they
+ *     pass through, as channels 6 and above always do.
+ * Workspace: dl_project_workspace_bytes, unchanged.  Refusals are dl_project's, before any launch.
+ */
+int dl_project_rotated(const float* pts, int64_t pts_cs, int64_t n_cols, const int32_t* offs, int32_t S, int32_t C,
+                       int32_t max_n, const dl_sensor* sensor, float* image4, float* aux, float* packed,
+                       float* packed_aux, int32_t* pix2pt, void* workspace, int32_t* kept, float* uvr,
+                       const float* rot, dl_stream stream);
+
+/*
+ * The rotations of one augmented training step from uniform draws, one tiny launch (additive: the ABI number stays).
+ *   draws [B][4] fp32 in [0, 1) (device): 0..2 the direction, 3 the angle;  rot [2B][9] out, the layout dl_project_rotated reads for a
+ *   batch stored as b0.scan_1, b0.scan_2, b1.scan_1, ...
+ * Row 2b is the exact identity (scan 1 is never rotated).  Row 2b+1 is Rodrigues' matrix cos(a) I + sin(a) [d]x + (1 - cos(a)) d d^T of
+ * the unit axis d = (0, 0, 1) when only_yaw, else draws 0..2 normalised (the reference draws them in [0, 1): every axis lies in the
+ * positive octant -- kept), and the angle a = (draw 3 - 0.5) * magnitude_rad, so |a| <= magnitude_rad / 2.  a == 0 (and three zero
+ * draws: no axis) give the exact identity; only_yaw writes row and column 2 as exact 0 / 1.  Entries are within 1e-6 of the float64
+ * evaluation (a dozen fp32 operations on values <= 1, sinf / cosf at a few ulp).
+ */
+int dl_rotations_from_draws(const float* draws, int32_t B, int32_t only_yaw, float magnitude_rad, float* rot, dl_stream stream);
 
 /*
  * The same projection from RAW POINT RECORDS, with the reference node's filter applied inside the vote (additive: the ABI number
