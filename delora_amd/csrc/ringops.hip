@@ -22,11 +22,12 @@ __device__ __forceinline__ float act_fwd(float v, int act) {
   return v;
 }
 
-// dy/dv from the OUTPUT value y (tanh' = 1 - y^2, relu' = [y > 0])
-__device__ __forceinline__ float act_bwd(float y, int act) {
-  if (act == ACT_TANH) return 1.f - y * y;
-  if (act == ACT_RELU) return y <= 0.f ? 0.f : 1.f;
-  return 1.f;
+// g * dy/dv from the OUTPUT value y (tanh' = 1 - y^2, relu' = [y > 0]).  relu SELECTS, as torch's threshold_backward does: a dead unit
+// gives +0.0 whatever its gradient -- a product with 0 would keep the gradient's sign in the zero and turn an infinite one into NaN.
+__device__ __forceinline__ float act_bwd_mul(float g, float y, int act) {
+  if (act == ACT_TANH) return g * (1.f - y * y);
+  if (act == ACT_RELU) return y <= 0.f ? 0.f : g;
+  return g;
 }
 
 // Storage types: the kernels compute in fp32; under autocast the activations are stored as fp16 / bf16 (one rounding per
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(DL_BLOCK) void k_ring_act_pad_bwd(const T* __restri
   for (int u = 0; u < RING_UN; ++u) {
     const I i = base + (I)u * DL_BLOCK;
     if (i < total) {
-      const float d = s[u] * act_bwd(yv[u], act);
+      const float d = act_bwd_mul(s[u], yv[u], act);
       stf(grad_x, (int64_t)i, d);
       if (grad_res_padded) {
         const I r = i / (I)W;
@@ -204,7 +205,8 @@ extern "C" int dl_ring_act_pad_bwd(const float* grad_out, const float* y, int64_
 //
 // Semantics are those of the separate ops, including the arg-max rule of torch's max-pool (scan rows then columns, the
 // first strictly greater value wins, NaN propagates): the activation is monotonically non-decreasing, so a candidate
-// whose pre-activation value does not exceed the current best's cannot win and its activation is never evaluated.
+// whose pre-activation value lies BELOW the current best's cannot win and its activation is never evaluated.  (One that equals it
+// is evaluated: the scan starts from best_x = -inf with nothing evaluated yet, and a window of -inf pools to act(-inf), not to -inf.)
 // x: dense [rows][W], rows = N*C*H.  out: [rows][Wo + 2] (pooled map with one wrapped column on each side),
 // Wo = (W-1)/2 + 1.  win: [rows][Wo] position (0..8, row-major in the 3x3 window) of each maximum, for the backward.
 template <typename T>
@@ -228,7 +230,7 @@ __global__ __launch_bounds__(DL_BLOCK) void k_ring_act_pool_pad_fwd(const T* __r
       int ww = 2 * wo + dw;
       ww = ww < 0 ? ww + W : (ww >= W ? ww - W : ww);
       const float xv = ldf(row, ww);
-      if (!(xv <= best_x)) {
+      if (!(xv < best_x)) {
         const float a = rnd<T>(act_fwd(xv, act));
         if (a > best_a || a != a) {
           best_a = a;
@@ -282,7 +284,7 @@ __global__ __launch_bounds__(DL_BLOCK) void k_ring_act_pool_pad_bwd(const T* __r
         float gv = ldf(g, 1 + wo);
         if (wo == Wo - 1) gv += ldf(g, 0);
         if (wo == 0) gv += ldf(g, Wo + 1);
-        acc += gv * act_bwd(ldf(y, rr * Wq + 1 + wo), act);
+        acc += act_bwd_mul(gv, ldf(y, rr * Wq + 1 + wo), act);
       }
     }
   }
@@ -352,7 +354,10 @@ __global__ __launch_bounds__(DL_BLOCK) void k_ring_act_pool_pad_fwd_even(const f
     float am = act_fwd(xm, act);
     int k = k0;
     if (act == ACT_RELU) {
-      if (xm <= 0.f) k = stem_first_position(h);         // every activation in the window is 0: the first position wins
+      if (xm <= 0.f) {                                   // every activation in the window is a zero: the first position wins,
+        k = stem_first_position(h);                      // with ITS zero (-0.0 only for an input of -0.0; xm may be a later -0.0)
+        am = act_fwd(t[rr + (h > 0 ? 0 : 1)][0], act);
+      }
     } else if (act == ACT_TANH && am == am) {
       const float d = 1.f - am * am;
       const float thr = d < 1e-4f ? -INFINITY : xm - 24.f * fmaxf(6e-8f * fabsf(am), 1e-37f) / d;
@@ -424,7 +429,7 @@ __global__ __launch_bounds__(DL_BLOCK) void k_ring_act_pool_pad_bwd_even(const f
       float gv = g[1 + wo];
       if (wo == Wo - 1) gv += g[0];
       if (wo == 0) gv += g[Wo + 1];
-      gv *= act_bwd(yr[1 + wo], act);
+      gv = act_bwd_mul(gv, yr[1 + wo], act);
       const int col = side == 0 ? c - 1 : 1;
 #pragma unroll
       for (int tt = 0; tt < STEM_RH; ++tt) {
