@@ -214,7 +214,165 @@ int forward_args(const char* who, const void* prepared, const float* image_prev,
   return DL_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same walk with the trunk in half precision (the *_h entry points): what ResNetModified.pooled_features_drop does inside
+// torch.autocast in eval mode -- fp32 interleave and conv1, the pooling that writes half precision (the Python path pools in fp32 and
+// casts: the same bits), every trunk layer on dl_conv2d_nhwc_h (one kernel family, so no per-shape routing to mirror), the fp32 pooled
+// feature from dl_mean_hw_nhwc_h, fp32 heads.  The prepared buffer holds w_fwd [taps][K][C] of every trunk convolution, in weight order
+// (w1, w2, wd per block), each at a 256-byte boundary; conv1 and the heads read the fp32 parameters.
+int dtype_check(const char* who, int dtype) {
+  if (dtype != DL_DTYPE_F16 && dtype != DL_DTYPE_BF16)
+    return dl_fail(DL_ERR_UNSUPPORTED, "%s: dtype=%d is not served (1 DL_DTYPE_F16, 2 DL_DTYPE_BF16; fp32 is the family without _h)", who, dtype);
+  return DL_OK;
+}
+
+inline size_t w_fwd_bytes(int taps, int k, int c) { return align_up((size_t)taps * k * c * 2); }
+
+// Four rotating slots as in the fp32 plan: the two stem slots hold fp32 (and later whatever half tensor a block puts there), everything
+// behind the pooling is half.  No fp32 pooled map, no window plane, no split-K scratch.
+PosePlan pose_plan_h(const dl_pose_net* net, int B, int H, int W) {
+  PosePlan p;
+  memset(&p, 0, sizeof(p));
+  auto hold = [&](int slot, size_t bytes) { if (bytes > p.slot_bytes[slot]) p.slot_bytes[slot] = bytes; };
+  hold(0, (size_t)B * H * W * 8 * 4);
+  hold(1, (size_t)B * H * (W / 2) * 64 * 4);
+  hold(2, (size_t)B * H * (W / 4) * 64 * 2);
+  int s = 2, h = H, w = W / 4;
+  for (int i = 0; i < net->n_blocks; ++i) {
+    const dl_pose_block& b = net->blocks[i];
+    const int ho = ceil_div(h, b.stride_h), wo = ceil_div(w, b.stride_w);
+    const size_t out = (size_t)B * ho * wo * b.cout * 2;
+    hold((s + 1) & 3, out);
+    if (b.has_downsample) hold((s + 2) & 3, out);
+    hold((s + 3) & 3, out);
+    p.prepared_bytes += w_fwd_bytes(9, b.cout, b.cin) + w_fwd_bytes(9, b.cout, b.cout) + (b.has_downsample ? w_fwd_bytes(1, b.cout, b.cin) : 0);
+    s = (s + 3) & 3; h = ho; w = wo;
+  }
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { const size_t at = off; off += align_up(bytes); return at; };
+  for (int i = 0; i < 4; ++i) p.slot_off[i] = carve(p.slot_bytes[i]);
+  p.feat_off = carve((size_t)B * net->F * 4);
+  p.a1_off = carve((size_t)B * net->R * 4);
+  p.a2_off = carve((size_t)B * 2 * net->Hd * 4);
+  p.rot_off = carve((size_t)B * 4 * 4);
+  p.norm_off = carve(4);
+  p.total = off;
+  return p;
+}
+
+int pose_forward_h(const char* who, const dl_pose_net* net, int dtype, const PosePlan& p, const void* prepared, const float* image_prev, int64_t prev_ss,
+                   const float* image_cur, int64_t cur_ss, int B, int H, int W, void* workspace, float* translation, float* quaternion, float* T,
+                   dl_stream stream) {
+  char* const ws = (char*)workspace;
+  void* slot[4];
+  for (int i = 0; i < 4; ++i) slot[i] = ws + p.slot_off[i];
+  const int act = net->act;
+  hipStream_t st = (hipStream_t)stream;
+  // 1. the transposing gather, 2. conv1 + activation in fp32, 3. the pooling, fp32 -> half
+  const uint32_t total = (uint32_t)B * H * W;
+  hipLaunchKernelGGL(k_interleave_pair, dim3((total + DL_BLOCK - 1) / DL_BLOCK), dim3(DL_BLOCK), 0, st, (const uint32_t*)image_prev, (size_t)prev_ss,
+                     (const uint32_t*)image_cur, (size_t)cur_ss, (uint32_t)(H * W), total, (u32x4i*)slot[0]);
+  if (int rc = dl_check_launch(who)) return rc;
+  if (int rc = at_layer(who, "conv1", -1, dl_conv2d_nhwc_f32((const float*)slot[0], net->conv1_w, (float*)slot[1], nullptr, nullptr, B, H, W, 8, 64, 3, 1, 2,
+                                                            0, act, DL_CONV_ACT, stream)))
+    return rc;
+  if (int rc = at_layer(who, "pooling", -1, dl_pool3x3s12_nhwc_fwd_h((const float*)slot[1], B, H, W / 2, 64, dtype, slot[2], stream))) return rc;
+  // 4. the residual blocks on the prepared half-precision weights
+  const char* u = (const char*)prepared;
+  int s = 2, h = H, w = W / 4;
+  for (int i = 0; i < net->n_blocks; ++i) {
+    const dl_pose_block& b = net->blocks[i];
+    const int ho = ceil_div(h, b.stride_h), wo = ceil_div(w, b.stride_w);
+    const void* x = slot[s];
+    void *y1 = slot[(s + 1) & 3], *sc = slot[(s + 2) & 3], *y2 = slot[(s + 3) & 3];
+    const char *u1 = u, *u2 = u1 + w_fwd_bytes(9, b.cout, b.cin), *ud = u2 + w_fwd_bytes(9, b.cout, b.cout);
+    u = ud + (b.has_downsample ? w_fwd_bytes(1, b.cout, b.cin) : 0);
+    int rc = dl_conv2d_nhwc_h(x, u1, y1, nullptr, nullptr, B, h, w, b.cin, b.cout, 3, b.stride_h, b.stride_w, 0, dtype, act, DL_CONV_ACT, stream);
+    if ((rc = at_layer(who, "w1", i, rc))) return rc;
+    const void* shortcut = x;
+    if (b.has_downsample) {
+      rc = dl_conv2d_nhwc_h(x, ud, sc, nullptr, nullptr, B, h, w, b.cin, b.cout, 1, b.stride_h, b.stride_w, 0, dtype, 0, 0, stream);
+      if ((rc = at_layer(who, "wd", i, rc))) return rc;
+      shortcut = sc;
+    }
+    rc = dl_conv2d_nhwc_h(y1, u2, y2, shortcut, nullptr, B, ho, wo, b.cout, b.cout, 3, 1, 1, 0, dtype, act, DL_CONV_ADD | DL_CONV_ACT, stream);
+    if ((rc = at_layer(who, "w2", i, rc))) return rc;
+    s = (s + 3) & 3; h = ho; w = wo;
+  }
+  // 5. global average pooling to the fp32 feature, 6. fc + heads + the whole-batch quaternion norm, 7. quaternion -> T: fp32 as ever
+  float* feat = (float*)(ws + p.feat_off);
+  if (int rc = at_layer(who, "pooled feature", -1, dl_mean_hw_nhwc_h(slot[s], B, h * w, net->F, dtype, feat, stream))) return rc;
+  if (int rc = at_layer(who, "heads", -1, dl_heads_fwd(feat, &net->heads, B, net->F, net->R, net->Hd, act, (float*)(ws + p.a1_off), (float*)(ws + p.a2_off),
+                                                        (float*)(ws + p.rot_off), translation, quaternion, (float*)(ws + p.norm_off), stream)))
+    return rc;
+  return at_layer(who, "T", -1, dl_quat_to_T_fwd(translation, quaternion, B, 1e-12f, T, stream));
+}
+
+// dtype DL_DTYPE_F32: the fp32 plan and walk; else the half-precision ones (the streaming calls below serve both families)
+inline PosePlan plan_for(const dl_pose_net* net, int dtype, int B, int H, int W) {
+  return dtype == DL_DTYPE_F32 ? pose_plan(net, B, H, W) : pose_plan_h(net, B, H, W);
+}
+inline int forward_for(const char* who, const dl_pose_net* net, int dtype, const PosePlan& p, const void* prepared, const float* image_prev,
+                       const float* image_cur, int H, int W, void* workspace, float* translation, float* quaternion, float* T, dl_stream stream) {
+  const int64_t ss = (int64_t)4 * H * W;
+  if (dtype == DL_DTYPE_F32) return pose_forward(who, net, p, prepared, image_prev, ss, image_cur, ss, 1, H, W, workspace, translation, quaternion, T, stream);
+  return pose_forward_h(who, net, dtype, p, prepared, image_prev, ss, image_cur, ss, 1, H, W, workspace, translation, quaternion, T, stream);
+}
+
 }  // namespace
+
+/* see include/delora_hip.h */
+extern "C" size_t dl_pose_net_prepared_bytes_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype) {
+  const char* who = "dl_pose_net_prepared_bytes_h";
+  if (dtype_check(who, dtype) || pose_check(who, net, B, H, W)) return 0;
+  return pose_plan_h(net, B, H, W).prepared_bytes;
+}
+
+/* see include/delora_hip.h */
+extern "C" size_t dl_pose_net_workspace_bytes_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype) {
+  const char* who = "dl_pose_net_workspace_bytes_h";
+  if (dtype_check(who, dtype) || pose_check(who, net, B, H, W)) return 0;
+  return pose_plan_h(net, B, H, W).total;
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_pose_net_prepare_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype, void* prepared, dl_stream stream) {
+  const char* who = "dl_pose_net_prepare_h";
+  if (int rc = dtype_check(who, dtype)) return rc;
+  if (int rc = pose_check(who, net, B, H, W)) return rc;
+  if (!prepared || ((uintptr_t)prepared & (kAlign - 1))) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: prepared must be a 256-byte aligned buffer", who);
+  // every trunk convolution in weight order (w1, w2, wd per block), forward layout only, DL_CONVH_BATCH per launch
+  dl_convh_layer layers[3 * DL_POSE_NET_MAX_BLOCKS];
+  int n = 0;
+  char* u = (char*)prepared;
+  auto put = [&](const float* w, int taps, int k, int c) {
+    layers[n++] = dl_convh_layer{w, u, nullptr, k, taps, c};
+    u += w_fwd_bytes(taps, k, c);
+  };
+  for (int i = 0; i < net->n_blocks; ++i) {
+    const dl_pose_block& b = net->blocks[i];
+    put(b.w1, 9, b.cout, b.cin);
+    put(b.w2, 9, b.cout, b.cout);
+    if (b.has_downsample) put(b.wd, 1, b.cout, b.cin);
+  }
+  for (int i0 = 0; i0 < n; i0 += DL_CONVH_BATCH) {
+    const int m = n - i0 < DL_CONVH_BATCH ? n - i0 : DL_CONVH_BATCH;
+    if (int rc = at_layer(who, "half-precision weights", -1, dl_conv_weights_batch_h(layers + i0, m, dtype, stream))) return rc;
+  }
+  return DL_OK;
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_pose_net_forward_h(const dl_pose_net* net, const void* prepared, const float* image_prev, int64_t prev_ss, const float* image_cur,
+                                     int64_t cur_ss, int32_t B, int32_t H, int32_t W, int32_t dtype, void* workspace, float* translation,
+                                     float* quaternion, float* T, dl_stream stream) {
+  const char* who = "dl_pose_net_forward_h";
+  if (int rc = dtype_check(who, dtype)) return rc;
+  if (int rc = pose_check(who, net, B, H, W)) return rc;
+  if (int rc = forward_args(who, prepared, image_prev, prev_ss, image_cur, cur_ss, H, W, workspace, translation, quaternion, T)) return rc;
+  const PosePlan p = pose_plan_h(net, B, H, W);
+  return pose_forward_h(who, net, dtype, p, prepared, image_prev, prev_ss, image_cur, cur_ss, B, H, W, workspace, translation, quaternion, T, stream);
+}
 
 /* see include/delora_hip.h */
 extern "C" size_t dl_pose_net_prepared_bytes(const dl_pose_net* net, int32_t B, int32_t H, int32_t W) {
@@ -271,22 +429,32 @@ static int odometry_check(const char* who, const dl_pose_net* net, const dl_sens
   return pose_check(who, net, 1, sensor->H, sensor->W);
 }
 
-/* see include/delora_hip.h */
-extern "C" size_t dl_odometry_workspace_bytes(const dl_pose_net* net, const dl_sensor* sensor, int32_t max_points, int32_t H, int32_t W) {
-  const char* who = "dl_odometry_workspace_bytes";
+// dl_odometry_workspace_bytes (dtype DL_DTYPE_F32) and dl_odometry_workspace_bytes_h
+static size_t odometry_workspace(const char* who, const dl_pose_net* net, int dtype, const dl_sensor* sensor, int32_t max_points, int32_t H, int32_t W) {
   if (odometry_check(who, net, sensor)) return 0;
   if (H != sensor->H || W != sensor->W || max_points < 0) {
     dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: H=%d W=%d must be the sensor's %dx%d, max_points=%d not negative", who, H, W, sensor->H, sensor->W, max_points);
     return 0;
   }
-  return pose_plan(net, 1, H, W).total + align_up((size_t)H * W * 4) + align_up(dl_project_workspace_bytes(1, H, W, max_points, 3));
+  return plan_for(net, dtype, 1, H, W).total + align_up((size_t)H * W * 4) + align_up(dl_project_workspace_bytes(1, H, W, max_points, 3));
 }
 
 /* see include/delora_hip.h */
-extern "C" int dl_odometry_push(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs, int32_t n_points,
-                                int32_t* offs, const float* image_prev, float* image_cur, void* workspace, float* translation, float* quaternion,
-                                float* T, dl_stream stream) {
-  const char* who = "dl_odometry_push";
+extern "C" size_t dl_odometry_workspace_bytes(const dl_pose_net* net, const dl_sensor* sensor, int32_t max_points, int32_t H, int32_t W) {
+  return odometry_workspace("dl_odometry_workspace_bytes", net, DL_DTYPE_F32, sensor, max_points, H, W);
+}
+
+/* see include/delora_hip.h */
+extern "C" size_t dl_odometry_workspace_bytes_h(const dl_pose_net* net, const dl_sensor* sensor, int32_t max_points, int32_t H, int32_t W, int32_t dtype) {
+  const char* who = "dl_odometry_workspace_bytes_h";
+  if (dtype_check(who, dtype)) return 0;
+  return odometry_workspace(who, net, dtype, sensor, max_points, H, W);
+}
+
+// dl_odometry_push (dtype DL_DTYPE_F32) and dl_odometry_push_h
+static int odometry_push(const char* who, int dtype, const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs,
+                         int32_t n_points, int32_t* offs, const float* image_prev, float* image_cur, void* workspace, float* translation,
+                         float* quaternion, float* T, dl_stream stream) {
   if (int rc = odometry_check(who, net, sensor)) return rc;
   const int H = sensor->H, W = sensor->W;
   if (!offs || !image_cur || !workspace || (!pts && n_points > 0)) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument (pts, offs, image_cur, workspace)", who);
@@ -295,7 +463,7 @@ extern "C" int dl_odometry_push(const dl_pose_net* net, const void* prepared, co
   if (((uintptr_t)image_cur & 3) || ((uintptr_t)offs & 3)) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: image_cur / offs are not 4-byte aligned", who);
   if (image_prev)
     if (int rc = forward_args(who, prepared, image_prev, (int64_t)4 * H * W, image_cur, (int64_t)4 * H * W, H, W, workspace, translation, quaternion, T)) return rc;
-  const PosePlan p = pose_plan(net, 1, H, W);
+  const PosePlan p = plan_for(net, dtype, 1, H, W);
   char* const ws = (char*)workspace;
   int32_t* pix2pt = (int32_t*)(ws + p.total);
   void* project_ws = ws + p.total + align_up((size_t)H * W * 4);
@@ -305,14 +473,30 @@ extern "C" int dl_odometry_push(const dl_pose_net* net, const void* prepared, co
                                                           project_ws, nullptr, nullptr, stream)))
     return rc;
   if (!image_prev) return DL_OK;
-  return pose_forward(who, net, p, prepared, image_prev, (int64_t)4 * H * W, image_cur, (int64_t)4 * H * W, 1, H, W, workspace, translation, quaternion, T, stream);
+  return forward_for(who, net, dtype, p, prepared, image_prev, image_cur, H, W, workspace, translation, quaternion, T, stream);
 }
 
 /* see include/delora_hip.h */
-extern "C" int dl_odometry_push_records(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records, int32_t n_records,
-                                        const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur, void* workspace,
-                                        float* translation, float* quaternion, float* T, dl_stream stream) {
-  const char* who = "dl_odometry_push_records";
+extern "C" int dl_odometry_push(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs, int32_t n_points,
+                                int32_t* offs, const float* image_prev, float* image_cur, void* workspace, float* translation, float* quaternion,
+                                float* T, dl_stream stream) {
+  return odometry_push("dl_odometry_push", DL_DTYPE_F32, net, prepared, sensor, pts, pts_cs, n_points, offs, image_prev, image_cur, workspace, translation,
+                       quaternion, T, stream);
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_odometry_push_h(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs, int32_t n_points,
+                                  int32_t* offs, const float* image_prev, float* image_cur, int32_t dtype, void* workspace, float* translation,
+                                  float* quaternion, float* T, dl_stream stream) {
+  const char* who = "dl_odometry_push_h";
+  if (int rc = dtype_check(who, dtype)) return rc;
+  return odometry_push(who, dtype, net, prepared, sensor, pts, pts_cs, n_points, offs, image_prev, image_cur, workspace, translation, quaternion, T, stream);
+}
+
+// dl_odometry_push_records (dtype DL_DTYPE_F32) and dl_odometry_push_records_h
+static int odometry_push_records(const char* who, int dtype, const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records,
+                                 int32_t n_records, const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur,
+                                 void* workspace, float* translation, float* quaternion, float* T, dl_stream stream) {
   if (int rc = odometry_check(who, net, sensor)) return rc;
   const int H = sensor->H, W = sensor->W;
   if (!offs || !image_cur || !workspace || !layout || (!records && n_records > 0))
@@ -324,7 +508,7 @@ extern "C" int dl_odometry_push_records(const dl_pose_net* net, const void* prep
   if (image_prev)
     if (int rc = forward_args(who, prepared, image_prev, (int64_t)4 * H * W, image_cur, (int64_t)4 * H * W, H, W, workspace, translation, quaternion, T)) return rc;
   // workspace: the forward's (B = 1) | pix2pt [H*W] int32 | the key plane -- dl_odometry_workspace_bytes with max_points = 0
-  const PosePlan p = pose_plan(net, 1, H, W);
+  const PosePlan p = plan_for(net, dtype, 1, H, W);
   char* const ws = (char*)workspace;
   int32_t* pix2pt = (int32_t*)(ws + p.total);
   void* project_ws = ws + p.total + align_up((size_t)H * W * 4);
@@ -334,5 +518,23 @@ extern "C" int dl_odometry_push_records(const dl_pose_net* net, const void* prep
                                                                   project_ws, nullptr, nullptr, stream)))
     return rc;
   if (!image_prev) return DL_OK;
-  return pose_forward(who, net, p, prepared, image_prev, (int64_t)4 * H * W, image_cur, (int64_t)4 * H * W, 1, H, W, workspace, translation, quaternion, T, stream);
+  return forward_for(who, net, dtype, p, prepared, image_prev, image_cur, H, W, workspace, translation, quaternion, T, stream);
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_odometry_push_records(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records, int32_t n_records,
+                                        const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur, void* workspace,
+                                        float* translation, float* quaternion, float* T, dl_stream stream) {
+  return odometry_push_records("dl_odometry_push_records", DL_DTYPE_F32, net, prepared, sensor, records, n_records, layout, offs, image_prev, image_cur,
+                               workspace, translation, quaternion, T, stream);
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_odometry_push_records_h(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records, int32_t n_records,
+                                          const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur, int32_t dtype,
+                                          void* workspace, float* translation, float* quaternion, float* T, dl_stream stream) {
+  const char* who = "dl_odometry_push_records_h";
+  if (int rc = dtype_check(who, dtype)) return rc;
+  return odometry_push_records(who, dtype, net, prepared, sensor, records, n_records, layout, offs, image_prev, image_cur, workspace, translation,
+                               quaternion, T, stream);
 }

@@ -12,6 +12,7 @@
 // channels are read whole by 16 neighbouring lanes).  Both kernels are HBM streams: 134 + 67 + 17 MB forward and
 // 67 + 17 + 134 + 134 MB backward at batch 8, 64x2048 input.
 #include "common.h"
+#include "convh_common.h"         // ch_f2h: the one fp32 -> F16 / BF16 conversion (the half-precision pooling below)
 
 #define ST_TANH 1
 #define ST_RELU 2
@@ -49,6 +50,47 @@ __global__ __launch_bounds__(DL_BLOCK) void k_pool_nhwc_fwd(const float* __restr
   }
   *reinterpret_cast<f32x4s*>(y + (size_t)i * 4) = best;
   *reinterpret_cast<uint32_t*>(win + (size_t)i * 4) = (uint32_t)k0 | ((uint32_t)k1 << 8) | ((uint32_t)k2 << 16) | ((uint32_t)k3 << 24);
+}
+
+// The same pooling for the half-precision inference walk (csrc/infer.hip): the maximum leaves in F16 / BF16 -- rounded by ch_f2h, the
+// conversion of dl_cast_f32_to_h, so the result is k_pool_nhwc_fwd followed by that cast, bit for bit -- and no window plane is
+// written.  One thread = one pooled pixel x 8 channels: two 16-byte loads per window position, one 16-byte store (a 64-channel pixel
+// is read whole by 8 neighbouring lanes).  A pure HBM stream: per pooled pixel 2 x 256 B of new input and 128 B out.
+template <bool F16>
+__global__ __launch_bounds__(DL_BLOCK) void k_pool_nhwc_fwd_h(const float* __restrict__ a, int H, int Wc, int C8, uint32_t total,
+                                                              u16* __restrict__ y) {
+  const uint32_t i = blockIdx.x * DL_BLOCK + threadIdx.x;
+  if (i >= total) return;
+  const int Wp = Wc >> 1;
+  const uint32_t pix = i / (uint32_t)C8;                 // (n, r, q) of the pooled map
+  const int c8 = (int)(i - pix * (uint32_t)C8);
+  const uint32_t nr = pix / (uint32_t)Wp;                // n * H + r
+  const int q = (int)(pix - nr * (uint32_t)Wp);
+  const int r = (int)(nr % (uint32_t)H);
+  float best[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) best[e] = -INFINITY;
+#pragma unroll
+  for (int dh = -1; dh <= 1; ++dh) {
+    if (r + dh < 0 || r + dh >= H) continue;
+    const float* row = a + ((size_t)(nr + dh) * Wc) * (size_t)(8 * C8) + 8 * c8;
+#pragma unroll
+    for (int dw = -1; dw <= 1; ++dw) {
+      int j = 2 * q + dw;
+      j = j < 0 ? j + Wc : j;                            // 2q+1 <= Wc-1: only the left neighbour wraps
+      const f32x4s lo = *reinterpret_cast<const f32x4s*>(row + (size_t)j * (8 * C8));
+      const f32x4s hi = *reinterpret_cast<const f32x4s*>(row + (size_t)j * (8 * C8) + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (lo[e] > best[e] || lo[e] != lo[e]) best[e] = lo[e];
+        if (hi[e] > best[4 + e] || hi[e] != hi[e]) best[4 + e] = hi[e];
+      }
+    }
+  }
+  u16x8 o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = ch_f2h<F16>(best[e]);
+  reinterpret_cast<u16x8*>(y)[i] = o;
 }
 
 // Gradient of pool(act(.)) with respect to the conv1 PRE-activation at conv1-output pixel (row r of image-row index nr, column j),
@@ -293,6 +335,21 @@ extern "C" int dl_pool3x3s12_nhwc_fwd(const float* a, int32_t N, int32_t H, int3
   hipLaunchKernelGGL(k_pool_nhwc_fwd, dim3((total + DL_BLOCK - 1) / DL_BLOCK), dim3(DL_BLOCK), 0, (hipStream_t)stream, a, H, W,
                      C / 4, total, y, win);
   return dl_check_launch("dl_pool3x3s12_nhwc_fwd");
+}
+
+/* see include/delora_hip.h */
+extern "C" int dl_pool3x3s12_nhwc_fwd_h(const float* a, int32_t N, int32_t H, int32_t W, int32_t C, int32_t dtype, void* y, dl_stream stream) {
+  const char* what = "dl_pool3x3s12_nhwc_fwd_h";
+  if (!a || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad argument", what);
+  if (dtype != DL_DTYPE_F16 && dtype != DL_DTYPE_BF16)
+    return dl_fail(DL_ERR_UNSUPPORTED, "%s: dtype=%d not supported (1 DL_DTYPE_F16, 2 DL_DTYPE_BF16)", what, dtype);
+  if ((W & 1) || (C & 7) || (size_t)N * H * W * C >= ((size_t)1 << 32))
+    return dl_fail(DL_ERR_UNSUPPORTED, "%s: N=%d H=%d W=%d C=%d not supported (W even, C %% 8, < 2^32 elements)", what, N, H, W, C);
+  const uint32_t total = (uint32_t)((size_t)N * H * (W / 2) * (C / 8));
+  const dim3 grid((total + DL_BLOCK - 1) / DL_BLOCK);
+  if (dtype == DL_DTYPE_F16) hipLaunchKernelGGL(k_pool_nhwc_fwd_h<true>, grid, dim3(DL_BLOCK), 0, (hipStream_t)stream, a, H, W, C / 8, total, (u16*)y);
+  else hipLaunchKernelGGL(k_pool_nhwc_fwd_h<false>, grid, dim3(DL_BLOCK), 0, (hipStream_t)stream, a, H, W, C / 8, total, (u16*)y);
+  return dl_check_launch(what);
 }
 
 extern "C" int dl_pool3x3s12_nhwc_bwd(const float* g, const float* a, const int8_t* win, int32_t N, int32_t H, int32_t W,

@@ -114,9 +114,19 @@ class NativePoseNet(object):
     The struct points INTO the model's parameters (conv1, whose parameter keeps torch's default layout, is the one copy): an in-place
     weight update is seen by the stem, the strided and 1x1 layers and the heads at the next forward pass, and by the Winograd layers
     after the next ``prepare()``.  ``prepared`` / ``workspace``: optional caller-owned fp32 / uint8 CUDA tensors of at least
-    ``prepared_bytes`` / ``workspace_bytes`` bytes, 256-byte aligned (tests carve them out of a poisoned arena)."""
+    ``prepared_bytes`` / ``workspace_bytes`` bytes, 256-byte aligned (tests carve them out of a poisoned arena).
 
-    def __init__(self, model, B, H, W, prepared=None, workspace=None, own_workspace=True):
+    ``dtype``: ``torch.bfloat16`` / ``torch.float16`` bind the half-precision family (``dl_pose_net_prepare_h`` / ``dl_pose_net_forward_h``):
+    the trunk runs on the kernels of ``torch.autocast`` training, with EVERY trunk weight converted once by ``prepare()`` into
+    ``prepared`` (a uint8 buffer of ``prepared_bytes``) -- the model's eval forward inside ``torch.autocast(dtype=...)``, bit for bit,
+    without its per-call weight conversion.  Images, parameters and outputs stay fp32."""
+
+    def __init__(self, model, B, H, W, prepared=None, workspace=None, own_workspace=True, dtype=torch.float32):
+        if dtype != torch.float32 and dtype not in ring_conv.DTYPE_CODE:
+            raise ValueError(f"NativePoseNet: dtype {dtype} is not served (torch.float32, torch.bfloat16, torch.float16)")
+        self.dtype = dtype
+        self.dtype_code = ring_conv.DTYPE_CODE.get(dtype, 0)         # (0 = DL_DTYPE_F32: the family without _h)
+        self._h = ("_h", (self.dtype_code,)) if self.dtype_code else ("", ())
         why = why_unsupported(model, H, W, B)
         if why is not None:
             raise ValueError("NativePoseNet: " + why)
@@ -133,6 +143,8 @@ class NativePoseNet(object):
         self._net_p = ctypes.cast(ctypes.pointer(self.net), ctypes.c_void_p)
         self.prepared_bytes = self._size("dl_pose_net_prepared_bytes")
         self.workspace_bytes = self._size("dl_pose_net_workspace_bytes")
+        if prepared is None and self.dtype_code:
+            prepared = torch.empty((self.prepared_bytes,), dtype=torch.uint8, device=self.device)
         self.prepared = prepared if prepared is not None else torch.empty((self.prepared_bytes // 4,), dtype=torch.float32, device=self.device)
         if workspace is None and own_workspace:
             workspace = torch.empty((self.workspace_bytes,), dtype=torch.uint8, device=self.device)
@@ -143,7 +155,8 @@ class NativePoseNet(object):
         self.prepare()
 
     def _size(self, fn):
-        n = int(getattr(self.lib, fn)(self._net_p, self.B, self.H, self.W))
+        fn += self._h[0]
+        n = int(getattr(self.lib, fn)(self._net_p, self.B, self.H, self.W, *self._h[1]))
         if not n:
             raise _lib.DeloraHipError(f"{fn}: {(self.lib.dl_last_error() or b'').decode()}")
         return n
@@ -153,9 +166,10 @@ class NativePoseNet(object):
         return why_unsupported(model, H, W, B) is None
 
     def prepare(self):
-        """The Winograd-domain weights of the stride-1 3x3 layers from the parameters as they are NOW (one launch)."""
-        _lib.check(self.lib.dl_pose_net_prepare(self._net_p, self.B, self.H, self.W, ring_conv._ptr(self.prepared), ring_conv._stream()),
-                   "dl_pose_net_prepare")
+        """The Winograd-domain weights of the stride-1 3x3 layers -- in half precision: the converted weights of every trunk layer --
+        from the parameters as they are NOW (one launch)."""
+        fn = "dl_pose_net_prepare" + self._h[0]
+        _lib.check(getattr(self.lib, fn)(self._net_p, self.B, self.H, self.W, *self._h[1], ring_conv._ptr(self.prepared), ring_conv._stream()), fn)
 
     def forward(self, image_prev, image_cur, out=None):
         """Two planar fp32 images ``[B,4,H,W]`` (dense inner dims, any scan stride) -> (translation [B,3], quaternion [B,4], T [B,4,4]);
@@ -174,9 +188,10 @@ class NativePoseNet(object):
         for t, s in zip(out, ((3,), (4,), (4, 4))):
             if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (self.B,) + s or not t.is_contiguous():
                 raise ValueError(f"out: expected contiguous fp32 CUDA {(self.B,) + s}, got {tuple(t.shape)}")
-        _lib.check(self.lib.dl_pose_net_forward(self._net_p, ring_conv._ptr(self.prepared), *ptrs, self.B, self.H, self.W, ring_conv._ptr(self.workspace),
-                                                ring_conv._ptr(translation), ring_conv._ptr(quaternion), ring_conv._ptr(T), ring_conv._stream()),
-                   "dl_pose_net_forward")
+        fn = "dl_pose_net_forward" + self._h[0]
+        _lib.check(getattr(self.lib, fn)(self._net_p, ring_conv._ptr(self.prepared), *ptrs, self.B, self.H, self.W, *self._h[1],
+                                         ring_conv._ptr(self.workspace), ring_conv._ptr(translation), ring_conv._ptr(quaternion), ring_conv._ptr(T),
+                                         ring_conv._stream()), fn)
         return translation, quaternion, T
 
 
@@ -184,10 +199,12 @@ class NativeOdometry(object):
     """``dl_odometry_push`` with its buffers: two ping-pong images, the offsets vector, the workspace (grown when a larger scan
     arrives) and the three outputs.  ``push(points [3,N])`` returns None for the first scan, then (translation [1,3], quaternion [1,4],
     T [1,4,4]) -- tensors that the next push overwrites.  ``image_t_1`` / ``image_t`` are the images of the last pair.
-    ``push_records(records, layout)`` is the same from raw point records (``dl_odometry_push_records``); the two may be mixed."""
+    ``push_records(records, layout)`` is the same from raw point records (``dl_odometry_push_records``); the two may be mixed.
+    ``dtype``: as ``NativePoseNet`` (``torch.bfloat16`` / ``torch.float16``: ``dl_odometry_push_h`` / ``dl_odometry_push_records_h``)."""
 
-    def __init__(self, model, sensor, max_points=1 << 17):
-        self.pose = NativePoseNet(model, 1, sensor.H, sensor.W, own_workspace=False)     # (the forward's workspace is the head of this one's)
+    def __init__(self, model, sensor, max_points=1 << 17, dtype=torch.float32):
+        self.pose = NativePoseNet(model, 1, sensor.H, sensor.W, own_workspace=False, dtype=dtype)     # (the forward's workspace is the head of this one's)
+        self._h = self.pose._h
         self.lib, self.sensor, dev = self.pose.lib, sensor, self.pose.device
         self.images = torch.zeros((2, 4, sensor.H, sensor.W), dtype=torch.float32, device=dev)
         self.offs = torch.zeros((2,), dtype=torch.int32, device=dev)
@@ -204,9 +221,10 @@ class NativeOdometry(object):
         if self.workspace is not None and n_points <= self.max_points:
             return
         self.max_points = max(int(n_points), 2 * self.max_points)
-        nbytes = int(self.lib.dl_odometry_workspace_bytes(self.pose._net_p, ctypes.byref(self.sensor.struct), self.max_points, self.sensor.H, self.sensor.W))
+        fn = "dl_odometry_workspace_bytes" + self._h[0]
+        nbytes = int(getattr(self.lib, fn)(self.pose._net_p, ctypes.byref(self.sensor.struct), self.max_points, self.sensor.H, self.sensor.W, *self._h[1]))
         if not nbytes:
-            raise _lib.DeloraHipError(f"dl_odometry_workspace_bytes: {(self.lib.dl_last_error() or b'').decode()}")
+            raise _lib.DeloraHipError(f"{fn}: {(self.lib.dl_last_error() or b'').decode()}")
         self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=self.pose.device)
 
     @property
@@ -226,9 +244,10 @@ class NativeOdometry(object):
             self.cur = 1 - self.cur                                  # the swap of the two image buffers
         prev = self.images[1 - self.cur] if self.count else None
         p = ring_conv._ptr
-        _lib.check(self.lib.dl_odometry_push(self.pose._net_p, p(self.pose.prepared), ctypes.byref(self.sensor.struct), p(points), points.stride(0), n,
-                                             p(self.offs), p(prev), p(self.images[self.cur]), p(self.workspace), p(self.translation), p(self.quaternion),
-                                             p(self.T), ring_conv._stream()), "dl_odometry_push")
+        fn = "dl_odometry_push" + self._h[0]
+        _lib.check(getattr(self.lib, fn)(self.pose._net_p, p(self.pose.prepared), ctypes.byref(self.sensor.struct), p(points), points.stride(0), n,
+                                         p(self.offs), p(prev), p(self.images[self.cur]), *self._h[1], p(self.workspace), p(self.translation),
+                                         p(self.quaternion), p(self.T), ring_conv._stream()), fn)
         self.count += 1
         return (self.translation, self.quaternion, self.T) if prev is not None else None
 
@@ -280,10 +299,10 @@ class NativeOdometry(object):
             self.cur = 1 - self.cur
         prev = self.images[1 - self.cur] if self.count else None
         p = ring_conv._ptr
-        _lib.check(self.lib.dl_odometry_push_records(self.pose._net_p, p(self.pose.prepared), ctypes.byref(self.sensor.struct), p(buf),
-                                                     nbytes // layout.point_step, ctypes.byref(layout), p(self.offs), p(prev), p(self.images[self.cur]),
-                                                     p(self.workspace), p(self.translation), p(self.quaternion), p(self.T), ring_conv._stream()),
-                   "dl_odometry_push_records")
+        fn = "dl_odometry_push_records" + self._h[0]
+        _lib.check(getattr(self.lib, fn)(self.pose._net_p, p(self.pose.prepared), ctypes.byref(self.sensor.struct), p(buf),
+                                         nbytes // layout.point_step, ctypes.byref(layout), p(self.offs), p(prev), p(self.images[self.cur]),
+                                         *self._h[1], p(self.workspace), p(self.translation), p(self.quaternion), p(self.T), ring_conv._stream()), fn)
         self.count += 1
         return (self.translation, self.quaternion, self.T) if prev is not None else None
 

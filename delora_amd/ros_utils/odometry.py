@@ -132,11 +132,21 @@ class ScanToScanOdometry(object):
     ``normalization_scaling``; anything else raises ``ValueError`` at construction.
 
     ``push_records`` takes a message as the driver delivers it (raw point records); on the native engine the node's filter runs inside
-    the library's projection (``dl_odometry_push_records``) and the host never touches the points."""
+    the library's projection (``dl_odometry_push_records``) and the host never touches the points.
 
-    def __init__(self, config, model=None, project_pair=None, engine="torch"):
+    ``precision``: "float32" (default), "bfloat16" or "float16" -- how a network trained under ``amp_dtype`` is served as it was trained.
+    Engine "torch" wraps the model call in ``torch.autocast("cuda", dtype=...)`` and takes ``.float()`` of its outputs; engine "native"
+    binds the half-precision family (``NativeOdometry(dtype=...)``: every trunk weight converted once).  ``config["amp_dtype"]`` is
+    deliberately NOT read: a caller who passes a training config gets fp32, as ever."""
+
+    PRECISIONS = {"float32": torch.float32, "bfloat16": torch.bfloat16, "float16": torch.float16}
+
+    def __init__(self, config, model=None, project_pair=None, engine="torch", precision="float32"):
         if engine not in ("torch", "native"):
             raise ValueError(f"engine must be 'torch' or 'native', got {engine!r}")
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"precision must be 'float32', 'bfloat16' or 'float16', got {precision!r}")
+        self.precision, self.dtype = precision, self.PRECISIONS[precision]
         self.engine = engine
         self.config = config
         self.device = config["device"]
@@ -166,7 +176,7 @@ class ScanToScanOdometry(object):
             why = native_infer.why_unsupported(self.model, self.sensor.H, self.sensor.W)
             if why is not None:
                 raise ValueError("engine 'native': " + why)
-            self.native = native_infer.NativeOdometry(self.model, self.sensor)
+            self.native = native_infer.NativeOdometry(self.model, self.sensor, dtype=self.dtype)
 
     def _result(self, T, translation_1):
         """The returned dict from ``T [1,4,4]`` and ``translation [1,3]`` (odometry_publisher.py:151-172)."""
@@ -206,7 +216,12 @@ class ScanToScanOdometry(object):
                 self.scaling_factor = self.normalize_input(input_1=current, input_2=previous)
             images = self.project_pair(previous, current, self.sensor)
             stacked = torch.cat((images[0:1], images[1:2]), dim=1)                # image_1 = previous, image_2 = current (:143)
-            translation_1, rot_repr_1 = self.model(stacked)
+            if self.dtype == torch.float32:
+                translation_1, rot_repr_1 = self.model(stacked)
+            else:
+                with torch.autocast("cuda", dtype=self.dtype):
+                    translation_1, rot_repr_1 = self.model(stacked)
+                translation_1, rot_repr_1 = translation_1.float(), rot_repr_1.float()
             T = self.geometry_handler.get_transformation_matrix_quaternion(
                 translation=translation_1, quaternion=rot_repr_1, device=self.device)
             quaternion = quaternion_from_matrix(T[0].double().cpu().numpy())

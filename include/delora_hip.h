@@ -726,6 +726,10 @@ int dl_conv2d_wgrad_batch_nhwc_h(const dl_wgrad_h_layer* layers, int32_t n, void
  *   the gradient through at a NaN.  g may hold anything: a gradient reaches only the element its window selected.
  */
 int dl_pool3x3s12_nhwc_fwd(const float* a, int32_t N, int32_t H, int32_t W, int32_t C, float* y, int8_t* win, dl_stream stream);
+/* The forward for inference in half precision: the same a -> y [N][H][W/2][C] in DL_DTYPE_F16 / DL_DTYPE_BF16 and NO window plane; equal,
+ * bit for bit, to dl_pool3x3s12_nhwc_fwd followed by dl_cast_f32_to_h (the same window rule, the same conversion).  W even, C % 8 == 0,
+ * fewer than 2^32 elements in a; any other dtype is DL_ERR_UNSUPPORTED. */
+int dl_pool3x3s12_nhwc_fwd_h(const float* a, int32_t N, int32_t H, int32_t W, int32_t C, int32_t dtype, void* y, dl_stream stream);
 int dl_pool3x3s12_nhwc_bwd(const float* g, const float* a, const int8_t* win, int32_t N, int32_t H, int32_t W, int32_t C,
                            int32_t act, float* g_conv, dl_stream stream);
 
@@ -935,6 +939,40 @@ int dl_odometry_push(const dl_pose_net* net, const void* prepared, const dl_sens
 int dl_odometry_push_records(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records, int32_t n_records,
                              const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur, void* workspace,
                              float* translation, float* quaternion, float* T, dl_stream stream);
+
+/*
+ * THE SAME IN HALF PRECISION (additive, ABI 10 as it stands): the *_h family serves a network trained under amp_dtype with the kernels it was
+ * trained on.  dtype is DL_DTYPE_F16 or DL_DTYPE_BF16 (anything else: DL_ERR_UNSUPPORTED, size functions 0); dl_pose_net, its fp32
+ * parameters, the scope, the refusals and every other argument are those of the fp32 family above.  The walk is what the Python eval
+ * path does inside torch.autocast (ResNetModified.pooled_features_drop, half branch, + OdometryModel._fused), the same launches on the
+ * same operands, hence the same bits: the interleave and conv1 + activation in fp32, dl_pool3x3s12_nhwc_fwd_h (fp32 -> half; the
+ * Python path pools in fp32 and casts, the same values), per block dl_conv2d_nhwc_h (+ activation), the 1x1 dl_conv2d_nhwc_h shortcut,
+ * dl_conv2d_nhwc_h (+ shortcut + activation), dl_mean_hw_nhwc_h to the fp32 feature, dl_heads_fwd and dl_quat_to_T_fwd in fp32.  Half
+ * precision has ONE kernel family for every layer, so the native and the Python walk agree at every shape.
+ *   PREPARED WEIGHTS: dl_pose_net_prepare_h converts EVERY trunk weight once (dl_conv_weights_batch_h, forward layout only) into
+ *   w_fwd [taps][K][C] arrays in weight order (w1, w2, wd per block), each at a 256-byte boundary of `prepared`
+ *   (dl_pose_net_prepared_bytes_h bytes = the sum of taps*K*C*2, each rounded up to 256).  conv1 and the heads keep reading the fp32
+ *   parameters.  Stale prepared weights run the whole trunk on the OLD weights: prepare again after every weight update.
+ *   WORKSPACE: dl_pose_net_workspace_bytes_h bytes: the four rotating slots (the two stem slots sized for fp32, everything behind the
+ *   pooling for half), the pooled feature and the heads' saved activations.  No fp32 pooled map, no window plane, no split-K scratch.
+ *   dl_odometry_workspace_bytes_h / dl_odometry_push_h / dl_odometry_push_records_h: the streaming calls on that forward; images,
+ *   points, records and outputs stay fp32.  Nothing is allocated per call, nothing synchronises, every call is capturable.
+ */
+size_t dl_pose_net_prepared_bytes_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype);
+int dl_pose_net_prepare_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype, void* prepared, dl_stream stream);
+size_t dl_pose_net_workspace_bytes_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype);
+int dl_pose_net_forward_h(const dl_pose_net* net, const void* prepared, const float* image_prev, int64_t prev_ss, const float* image_cur,
+                          int64_t cur_ss, int32_t B, int32_t H, int32_t W, int32_t dtype, void* workspace, float* translation,
+                          float* quaternion, float* T, dl_stream stream);
+size_t dl_odometry_workspace_bytes_h(const dl_pose_net* net, const dl_sensor* sensor, int32_t max_points, int32_t H, int32_t W,
+                                     int32_t dtype);
+int dl_odometry_push_h(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs,
+                       int32_t n_points, int32_t* offs, const float* image_prev, float* image_cur, int32_t dtype, void* workspace,
+                       float* translation, float* quaternion, float* T, dl_stream stream);
+int dl_odometry_push_records_h(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records,
+                               int32_t n_records, const dl_record_layout* layout, int32_t* offs, const float* image_prev,
+                               float* image_cur, int32_t dtype, void* workspace, float* translation, float* quaternion, float* T,
+                               dl_stream stream);
 
 /*
  * What the convolution dispatch would launch (for tests and tools; host only, nothing is enqueued): runs the matching entry point's

@@ -3,7 +3,10 @@
 // as INTEGRATION.md section C describes for a C or C++ caller.  The counterpart of the reference's inference node (bin/run_rosnode.py)
 // without ROS.
 //
-//   odometry_demo [--records <point_step> <off_x> <off_y> <off_z>] <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...
+//   odometry_demo [--half bf16|f16] [--records <point_step> <off_x> <off_y> <off_z>] <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...
+//
+// With --half the same program runs through the half-precision family (dl_pose_net_prepare_h, dl_odometry_push_h /
+// dl_odometry_push_records_h): the fp32 weight file is converted once by the prepare call, the trunk runs in bf16 / fp16.
 //
 // With --records the scan files are raw point records as a sensor driver writes them (fp32 x, y, z at the three byte offsets of
 // point_step-byte records; a KITTI .bin file is --records 16 0 4 8): they are uploaded as they are and pushed through
@@ -33,6 +36,7 @@
 #include "../delora_amd/csrc/stem.hip"
 #include "../delora_amd/csrc/pose.hip"
 #include "../delora_amd/csrc/heads.hip"
+#include "../delora_amd/csrc/convh.hip"
 #include "../delora_amd/csrc/infer.hip"
 
 #define HIP_OK(call)                                                                                         \
@@ -153,6 +157,15 @@ static std::vector<char> read_file(const char* path) {
 }
 
 int main(int argc, char** argv) {
+  // ---- the optional storage type of the trunk (DL_DTYPE_F32: the fp32 family)
+  int32_t half = DL_DTYPE_F32;
+  if (argc > 1 && !strcmp(argv[1], "--half")) {
+    if (argc < 3) die("--half needs bf16 or f16");
+    half = !strcmp(argv[2], "bf16") ? DL_DTYPE_BF16 : !strcmp(argv[2], "f16") ? DL_DTYPE_F16 : DL_DTYPE_F32;
+    if (half == DL_DTYPE_F32) die(std::string("--half: bf16 or f16 expected, got ") + argv[2]);
+    argc -= 2;
+    argv += 2;
+  }
   // ---- the optional record layout
   bool records = false;
   dl_record_layout layout = {12, 0, 4, 8, DL_RECORDS_DROP_ZERO | DL_RECORDS_MIN_RANGE, 0.3f};
@@ -171,7 +184,7 @@ int main(int argc, char** argv) {
     argv += 5;
   }
   if (argc < 5)
-    die("usage: odometry_demo [--records <point_step> <off_x> <off_y> <off_z>] <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...   (scans: "
+    die("usage: odometry_demo [--half bf16|f16] [--records <point_step> <off_x> <off_y> <off_z>] <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...   (scans: "
         "float32 [3][N], or raw records with --records)");
   const size_t unit = records ? (size_t)layout.point_step : 12;        // bytes per point in a scan file
   // ---- the weight file
@@ -251,10 +264,11 @@ int main(int argc, char** argv) {
   }
 
   // ---- buffers: all owned here, the library allocates nothing
-  const size_t prepared_bytes = dl_pose_net_prepared_bytes(&net, 1, H, W);
+  const size_t prepared_bytes = half ? dl_pose_net_prepared_bytes_h(&net, 1, H, W, half) : dl_pose_net_prepared_bytes(&net, 1, H, W);
   if (!prepared_bytes) die(std::string("dl_pose_net_prepared_bytes: ") + dl_last_error());
   // (the records path keeps no staging records: its workspace does not grow with the scan)
-  const size_t ws_bytes = dl_odometry_workspace_bytes(&net, &sensor, records ? 0 : (int32_t)max_points, H, W);
+  const size_t ws_bytes = half ? dl_odometry_workspace_bytes_h(&net, &sensor, records ? 0 : (int32_t)max_points, H, W, half)
+                               : dl_odometry_workspace_bytes(&net, &sensor, records ? 0 : (int32_t)max_points, H, W);
   if (!ws_bytes) die(std::string("dl_odometry_workspace_bytes: ") + dl_last_error());
   void *prepared = nullptr, *workspace = nullptr;
   float *images[2] = {nullptr, nullptr}, *d_pts = nullptr, *d_out = nullptr;
@@ -268,7 +282,8 @@ int main(int argc, char** argv) {
   HIP_OK(hipMalloc((void**)&d_out, 256));                              // translation [3] | quaternion [4] | T [16] at floats 0, 4, 8
   hipStream_t stream;
   HIP_OK(hipStreamCreate(&stream));
-  DL_OK_OR_DIE(dl_pose_net_prepare(&net, 1, H, W, prepared, stream));
+  if (half) DL_OK_OR_DIE(dl_pose_net_prepare_h(&net, 1, H, W, half, prepared, stream));
+  else DL_OK_OR_DIE(dl_pose_net_prepare(&net, 1, H, W, prepared, stream));
 
   FILE* out = fopen(argv[2], "w");
   if (!out) die(std::string("cannot write ") + argv[2]);
@@ -278,7 +293,14 @@ int main(int argc, char** argv) {
     const size_t n = scans[i].size() / unit;
     if (n) HIP_OK(hipMemcpyAsync(d_pts, scans[i].data(), n * unit, hipMemcpyHostToDevice, stream));
     if (i) cur = 1 - cur;                                            // the caller's swap of the two image buffers
-    if (records)
+    const float* prev = i ? images[1 - cur] : nullptr;
+    if (records && half)
+      DL_OK_OR_DIE(dl_odometry_push_records_h(&net, prepared, &sensor, d_pts, (int32_t)n, &layout, d_offs, prev, images[cur], half, workspace, d_out,
+                                              d_out + 4, d_out + 8, stream));
+    else if (half)
+      DL_OK_OR_DIE(dl_odometry_push_h(&net, prepared, &sensor, d_pts, (int64_t)n, (int32_t)n, d_offs, prev, images[cur], half, workspace, d_out, d_out + 4,
+                                      d_out + 8, stream));
+    else if (records)
       DL_OK_OR_DIE(dl_odometry_push_records(&net, prepared, &sensor, d_pts, (int32_t)n, &layout, d_offs, i ? images[1 - cur] : nullptr, images[cur],
                                             workspace, d_out, d_out + 4, d_out + 8, stream));
     else
