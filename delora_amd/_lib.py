@@ -155,6 +155,11 @@ SIGNATURES = {
     "dl_odometry_workspace_bytes_h": (_sz, [_vp, _SP, _i32, _i32, _i32, _i32]),
     "dl_odometry_push_h": (_i32, [_vp, _vp, _SP, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "dl_odometry_push_records_h": (_i32, [_vp, _vp, _SP, _vp, _i32, _RP, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "dl_stem_input_nhwc_h": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "dl_stem_conv1_h": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "dl_stem_pool_fwd_h": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dl_stem_wgrad_h_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dl_stem_wgrad_h": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dl_profile_begin": (_i32, [_i32, ctypes.c_char_p]),
     "dl_profile_end": (_i32, [_vp, _i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "dl_profile_pause": (_i32, [_i32]),

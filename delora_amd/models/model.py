@@ -39,6 +39,7 @@ class OdometryModel(torch.nn.Module):
             num_outputs=config["resnet_outputs"], use_dropout=config["use_dropout"], layers=config["layers"],
             factor_fewer_resnet_channels=config["factor_fewer_resnet_channels"], activation_fct=act,
             impl=config.get("cnn_impl", "auto"))
+        self.resnet.amp_stem = bool(config.get("amp_stem", False))       # the stem in the autocast dtype too (default: fp32)
         n_feat = config["resnet_outputs"]
         if config["use_single_mlp_at_output"]:           # model.py:59-72
             self.fully_connected_rot_trans = _mlp(act, [n_feat, 512, 512, 256, 64, 3 + 4])

@@ -74,6 +74,9 @@ class ResNetModified(torch.nn.Module):
         # otherwise; "modules" forces the latter, "hip" makes unsupported shapes an error.
         self.impl = impl
         self.use_dropout = bool(use_dropout)
+        # config key amp_stem (OdometryModel sets it): inside autocast the stem runs in the autocast dtype too (ring_conv.RingStemH)
+        # instead of fp32 in front of the half-precision trunk.  Off by default: it rounds the range image itself to 8 / 11 bits.
+        self.amp_stem = False
         self.dropout_p = 0.2                           # the reference's rate at all three sites (resnet_modified.py:33-38)
         widths = [int(c / factor_fewer_resnet_channels) for c in (64, 128, 256, 512)]
         self.inplanes = widths[0]
@@ -173,6 +176,19 @@ class ResNetModified(torch.nn.Module):
             return None
         return dtype if ring_conv.supported_h((N, Hin, Win // 4, C0), self._trunk_blocks()[0]) else None
 
+    def hip_half_stem_applicable(self, x):
+        """Whether the stem too runs in half precision (``ring_conv.RingStemH``): ``amp_stem`` is set, the half-precision trunk takes the
+        input (``hip_half_applicable``), conv1 is the 8 -> 64 layer, dropout is not active (its input mask lives in the fp32 copy) and
+        the image needs no gradient (the half stem computes none).  Returns the autocast dtype or None."""
+        if not self.amp_stem or self.dropout_active() or x.requires_grad:
+            return None
+        if self.conv1.in_channels != 8 or self.conv1.out_channels != 64:
+            return None
+        half = self.hip_half_applicable(x)
+        if half is None or x.dtype != torch.float32 or not ring_conv.stem_h_supported(tuple(x.shape), self.conv1.out_channels):
+            return None
+        return half
+
     def dropout_active(self):
         return self.use_dropout and self.training
 
@@ -206,6 +222,12 @@ class ResNetModified(torch.nn.Module):
         if half is not None:
             # autocast: fp32 stem (8 input channels: 0.4 ms), then layer1..layer4 + pooling on the half-precision MFMA kernels
             blocks, weights = self._trunk_blocks()
+            if self.hip_half_stem_applicable(x) is not None:
+                # amp_stem: conv1, the pooling and the fused weight gradient in the autocast dtype as well; no fp32 map, no cast launch
+                with torch.autocast("cuda", enabled=False):
+                    x0 = ring_conv.RingStemH.apply(x, self.conv1.weight, ring_conv.ACT[act], half)          # [N,H,W/4,C0] half
+                    feat = ring_conv.ring_trunk_h(x0, ring_conv.ACT[act], blocks, half, weights, x0_is_half=True)
+                return feat, None, None
             with torch.autocast("cuda", enabled=False):
                 d_ch = fc_scale = None
                 if self.dropout_active():

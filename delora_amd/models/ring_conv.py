@@ -1328,11 +1328,92 @@ class MeanHWActH(torch.autograd.Function):
         return g, None
 
 
-def ring_trunk_h(x0, act, blocks, dtype, weights, segments=None, channel_drop=None):
+def ring_trunk_h(x0, act, blocks, dtype, weights, segments=None, channel_drop=None, x0_is_half=False):
     """layer1..layer4 + global average pooling in half precision: x0 ``[N,H,W,C0]`` fp32 channels-last (the pooled stem output),
-    fp32 parameters in block order; returns the pooled features ``[N,C']`` in fp32."""
-    x = _run_segments(RingSegmentH, CastToHalf.apply(x0, dtype), act, blocks, list(weights), segments, False, channel_drop)
+    fp32 parameters in block order; returns the pooled features ``[N,C']`` in fp32.  ``x0_is_half``: x0 is already in ``dtype`` (the
+    output of ``RingStemH``) -- no ``CastToHalf`` launch, and the first segment's input gradient goes back in half as it is."""
+    if x0_is_half:
+        if x0.dtype != dtype:
+            raise TypeError(f"ring_trunk_h(x0_is_half=True): x0 is {x0.dtype}, the trunk runs in {dtype}")
+    else:
+        x0 = CastToHalf.apply(x0, dtype)
+    x = _run_segments(RingSegmentH, x0, act, blocks, list(weights), segments, False, channel_drop)
     return MeanHWActH.apply(x, act)
+
+
+def stem_input_h(x, dtype):
+    """The planar fp32 image ``[N,8,H,W]`` as channels-last half ``[N,H,W,8]`` (``dl_stem_input_nhwc_h``: one transposing, rounding copy)."""
+    lib = _lib.load()
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    x8h = torch.empty((N, H, W, 8), dtype=dtype, device=x.device)
+    _lib.check(lib.dl_stem_input_nhwc_h(_ptr(x), N, H, W, DTYPE_CODE[dtype], _ptr(x8h), _stream()), "dl_stem_input_nhwc_h")
+    return x8h
+
+
+def stem_conv1_h(x8h, w1, act):
+    """conv1 + activation on the half image: ``a [N,H,W/2,64]`` in the dtype of ``x8h``; ``w1`` the raw fp32 parameter ``[64,8,3,3]``."""
+    lib = _lib.load()
+    N, H, W, _ = x8h.shape
+    a = torch.empty((N, H, W // 2, 64), dtype=x8h.dtype, device=x8h.device)
+    _lib.check(lib.dl_stem_conv1_h(_ptr(x8h), _ptr(weight_storage(w1)), N, H, W, int(act), DTYPE_CODE[x8h.dtype], _ptr(a), _stream()),
+               "dl_stem_conv1_h")
+    return a
+
+
+def pool_fwd_h(a):
+    """Stem max-pooling of a half map ``[N,H,Wc,C]`` -> (y ``[N,H,Wc/2,C]`` in the same dtype, win int8)."""
+    lib = _lib.load()
+    N, H, Wc, C = a.shape
+    y = torch.empty((N, H, Wc // 2, C), dtype=a.dtype, device=a.device)
+    win = torch.empty((N, H, Wc // 2, C), dtype=torch.int8, device=a.device)
+    _lib.check(lib.dl_stem_pool_fwd_h(_ptr(a), N, H, Wc, C, DTYPE_CODE[a.dtype], _ptr(y), _ptr(win), _stream()), "dl_stem_pool_fwd_h")
+    return y, win
+
+
+def stem_h_supported(x_shape, out_channels):
+    """Whether ``RingStemH`` takes a planar input ``[N,8,H,W]``: the 8 -> 64 conv1, a width that halves twice, fewer than 2^31 elements
+    in conv1's output."""
+    N, C, H, W = x_shape
+    return C == 8 and out_channels == 64 and W % 4 == 0 and W >= 4 and H >= 1 and N >= 1 and N * H * W * 32 < (1 << 31)
+
+
+class RingStemH(torch.autograd.Function):
+    """``RingStem`` in half precision (csrc/stemh.hip): ``RingStemH.apply(x, w1, act, dtype)`` with the planar fp32 image ``[N,8,H,W]``
+    and the fp32 parameter ``w1 [64,8,3,3]`` -> the pooled map ``[N,H,W/4,64]`` in ``dtype``.  Forward: the rounding, transposing copy
+    (``x8h``), conv1 + activation on the half-precision MFMA with fp32 accumulation (``a``), the pooling on the half map (``y``, ``win``).
+    Saved: ``x8h``, ``a``, ``win``, ``w1`` -- half of what ``RingStem`` keeps.  Backward: the half gradient of ``y`` -> ``dw`` (fp32, laid
+    out as the parameter) in one fused launch pair, ``dl_stem_wgrad_h``.  The image gets NO gradient: callers keep inputs that require
+    one on the fp32 stem (``ResNetModified.hip_half_stem_applicable``), and asking for it here is an error, not a silent zero."""
+
+    @staticmethod
+    def forward(ctx, x, w1, act, dtype):
+        if not stem_h_supported(tuple(x.shape), w1.shape[0]) or x.dtype != torch.float32 or w1.dtype != torch.float32:
+            raise _lib.DeloraHipError(f"RingStemH does not take x {tuple(x.shape)} {x.dtype}, w1 {tuple(w1.shape)} {w1.dtype}")
+        if ctx.needs_input_grad[0]:
+            raise _lib.DeloraHipError("RingStemH computes no gradient with respect to the image; use RingStem")
+        x8h = stem_input_h(x, dtype)
+        a = stem_conv1_h(x8h, w1, act)
+        y, win = pool_fwd_h(a)
+        ctx.save_for_backward(x8h, a, win, w1)
+        ctx.act = int(act)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x8h, a, win, w1 = ctx.saved_tensors
+        lib = _lib.load()
+        N, H, W, _ = x8h.shape
+        nbytes = lib.dl_stem_wgrad_h_workspace_bytes(N, H, W)
+        if not nbytes:
+            raise _lib.DeloraHipError(f"dl_stem_wgrad_h does not support x8h {tuple(x8h.shape)}")
+        if g.dtype != a.dtype:
+            g = g.to(a.dtype)
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=x8h.device)
+        dw = torch.empty((64, 8, 3, 3), dtype=torch.float32, device=x8h.device)
+        _lib.check(lib.dl_stem_wgrad_h(_ptr(g.contiguous()), _ptr(a), _ptr(win), _ptr(x8h), N, H, W, ctx.act, DTYPE_CODE[a.dtype], _ptr(ws),
+                                       _ptr(dw), _stream()), "dl_stem_wgrad_h")
+        return None, (dw if tuple(dw.stride()) == tuple(w1.stride()) else grad_for(dw.permute(0, 2, 3, 1).contiguous(), w1)), None, None
 
 
 class RingTrunkH:

@@ -137,7 +137,9 @@ class ScanToScanOdometry(object):
     ``precision``: "float32" (default), "bfloat16" or "float16" -- how a network trained under ``amp_dtype`` is served as it was trained.
     Engine "torch" wraps the model call in ``torch.autocast("cuda", dtype=...)`` and takes ``.float()`` of its outputs; engine "native"
     binds the half-precision family (``NativeOdometry(dtype=...)``: every trunk weight converted once).  ``config["amp_dtype"]`` is
-    deliberately NOT read: a caller who passes a training config gets fp32, as ever."""
+    deliberately NOT read: a caller who passes a training config gets fp32, as ever.  ``config["amp_stem"]`` IS followed by engine
+    "torch" in half precision (the model is built from the config: conv1 then runs on rounded operands as in training); engine "native"
+    keeps conv1 in fp32 whatever the key says."""
 
     PRECISIONS = {"float32": torch.float32, "bfloat16": torch.bfloat16, "float16": torch.float16}
 

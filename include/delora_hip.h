@@ -743,6 +743,37 @@ int dl_stem_wgrad_f32(const float* g_pooled, const float* a, const int8_t* win, 
                       int32_t act, void* workspace, float* dw, dl_stream stream);
 
 /*
+ * The same stem in half precision (csrc/stemh.hip; the config key amp_stem under amp_dtype).  dtype is DL_DTYPE_F16 or DL_DTYPE_BF16,
+ * h(v) the round-to-nearest-even conversion of an fp32 value to it (the conversion of dl_cast_f32_to_h, torch's .to(dtype)).
+ *   dl_stem_input_nhwc_h  x_nchw [N][8][H][W] fp32 -> x8h [N][H][W][8] = h(x): the channels-last image, 16 bytes per pixel.
+ *   dl_stem_conv1_h       a [N][H][W/2][64] = h(act(sum over (r, s, c) of h(w1[k][r][s][c]) * x8h[n][y + r - 1][(2 wc + s - 1) mod W][c])):
+ *                         rows outside the image contribute zero, the width wraps around, the sum is accumulated in fp32 (every product
+ *                         of two half values is an fp32 number), act: 0 none, 1 tanh, 2 relu (the epilogue arithmetic of
+ *                         dl_conv2d_nhwc_h).  w1 is the RAW fp32 parameter in its channels-last storage [64][3][3][8], converted inside
+ *                         the kernel: no prepared buffer.
+ *   dl_stem_pool_fwd_h    a [N][H][Wc][C] half -> y [N][H][Wc/2][C] half and win int8, by the window rule of dl_pool3x3s12_nhwc_fwd
+ *                         (rows first, the first strictly greater value wins, the wrapped left column, its NaN / zero / infinity
+ *                         rules) on the half values: equal bit for bit, win included, to that pooling of float(a) followed by
+ *                         dl_cast_f32_to_h.  Wc even, C % 8 == 0.
+ *   dl_stem_wgrad_h       g_pooled [N][H][W/4][64] half, a, win (the two forward outputs), x8h -> dw [64][8][3][3] fp32 (the parameter's
+ *                         default layout) = sum over the pixels of gc * x8h with gc = h(act'(a) * (sum of g over the windows that
+ *                         selected the element, fp32)) built tile by tile in LDS and never written; fp32 accumulation, slab and wave
+ *                         sums in a fixed order, no atomics: the same bits from run to run.  a must be finite (as dl_stem_wgrad_f32).
+ *                         The workspace holds one [64][72] fp32 partial per slab: 64-pixel chunks of the W/2-wide rows, at most 512
+ *                         slabs -- the plan of dl_stem_wgrad_f32; bytes from dl_stem_wgrad_h_workspace_bytes (0 = shape refused).
+ * Refusals, before any launch, with dl_last_error naming the entry point and the field: a NULL pointer, a pointer that is not aligned
+ * (16 bytes for the half tensors, w1 and the workspace, 8 for win, 4 for x_nchw and dw), a non-positive size or an act outside 0..2
+ * are DL_ERR_INVALID_ARGUMENT; any other dtype, W % 4 != 0 (Wc odd, C % 8 != 0 for the pooling) and 2^31 or more elements in the
+ * largest tensor of the call are DL_ERR_UNSUPPORTED.  No call synchronises or copies to the host; every launch goes to `stream`.
+ */
+int dl_stem_input_nhwc_h(const float* x_nchw, int32_t N, int32_t H, int32_t W, int32_t dtype, void* x8h, dl_stream stream);
+int dl_stem_conv1_h(const void* x8h, const float* w1, int32_t N, int32_t H, int32_t W, int32_t act, int32_t dtype, void* a, dl_stream stream);
+int dl_stem_pool_fwd_h(const void* a, int32_t N, int32_t H, int32_t Wc, int32_t C, int32_t dtype, void* y, int8_t* win, dl_stream stream);
+size_t dl_stem_wgrad_h_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int dl_stem_wgrad_h(const void* g_pooled, const void* a, const int8_t* win, const void* x8h, int32_t N, int32_t H, int32_t W, int32_t act,
+                    int32_t dtype, void* workspace, float* dw, dl_stream stream);
+
+/*
  * The pose heads in seven launches (csrc/heads.hip): fc -> the two two-layer MLPs -> whole-batch quaternion norm, forward and backward
  * (reference src/models/resnet_modified.py:118-120, src/models/model.py:74-83, :114; torch autograd through them).  fp32.
  *   x [B][F] pooled feature; fc [R][F]; first layers [Hd][R]; last layers [4][Hd] (rotation), [3][Hd] (translation); 1 <= B <= 16;
