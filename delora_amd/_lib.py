@@ -30,6 +30,15 @@ class RecordLayout(ctypes.Structure):
 
 RECORDS_DROP_ZERO, RECORDS_MIN_RANGE = 1, 2          # DL_RECORDS_* of include/delora_hip.h
 
+
+class ScanGeometry(ctypes.Structure):
+    """``dl_scan_geometry`` of include/delora_hip.h: the caller-owned record beside one image buffer of ``dl_odometry_quality``."""
+    _fields_ = [("normals", ctypes.c_void_p), ("packed_image", ctypes.c_void_p), ("packed_normals", ctypes.c_void_p)]
+
+
+INFO_OK, INFO_TOO_FEW_PAIRS, INFO_UNOBSERVABLE = 0, 1, 2        # DL_INFO_* of include/delora_hip.h
+INFO_MIN_PIVOT = 1e-10
+
 _vp, _i32, _i64, _u32, _f32, _sz = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
                                     ctypes.c_float, ctypes.c_size_t)
 _SP = ctypes.POINTER(SensorStruct)
@@ -56,6 +65,8 @@ SIGNATURES = {
     "dl_icp_loss_partial": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _u32, _vp, _vp]),
     "dl_icp_loss_reduce": (_i32, [_vp, _i32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "dl_icp_loss_bwd": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "dl_icp_information_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dl_icp_information": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dl_ring_act_pool_pad_fwd": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dl_ring_act_pool_pad_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "dl_timer_create": (_i32, [ctypes.POINTER(ctypes.c_void_p)]),
@@ -155,6 +166,8 @@ SIGNATURES = {
     "dl_odometry_workspace_bytes_h": (_sz, [_vp, _SP, _i32, _i32, _i32, _i32]),
     "dl_odometry_push_h": (_i32, [_vp, _vp, _SP, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "dl_odometry_push_records_h": (_i32, [_vp, _vp, _SP, _vp, _i32, _RP, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "dl_odometry_quality_workspace_bytes": (_sz, [_SP, _i32, _i32]),
+    "dl_odometry_quality": (_i32, [_SP, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dl_stem_input_nhwc_h": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_stem_conv1_h": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "dl_stem_pool_fwd_h": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -23,25 +23,17 @@
 // HBM-bound: algorithmic traffic per source pixel = 24 B (p, n) + 4 B (correspondence) + 24 B (matched p_t, n_t)
 // = 52 B, all of it coalesced 16-byte loads.
 #include "common.h"
+#include "icp_stream.h"
 #include <hip/hip_ext.h>
 
 extern "C" int dl_icp_loss_partial_timed(const float*, int64_t, const float*, int64_t, const float*, int64_t, const int32_t*,
                                          const float*, int32_t, int32_t, int32_t, uint32_t, void*, void*, dl_stream);
 
-#define LOSS_PX 4            // consecutive pixels per lane (16-byte loads of every streamed plane)
 #define ACC_N 24            // po2pl: 0 rr, 1-3 r*nt, 4-12 r*nt p^T ; pl2pl: 13 ss, 14-22 G ; 23 K
 #define ACC_P2P 14          // 24 dd, 25-27 diff, 28-36 diff p^T, 37 K'
 #define ACC_MAX (ACC_N + ACC_P2P)
 #define ACC_PITCH 40        // floats per partial row
 
-#ifndef LOSS_WG_PER_SAMPLE
-#define LOSS_WG_PER_SAMPLE 128  // workgroups (4 waves each) per sample: 512 waves, 1 chunk per wave at 64x2048
-#endif
-static inline int loss_blocks(int HW) {
-  const int chunks = (HW + DL_WAVE * LOSS_PX - 1) / (DL_WAVE * LOSS_PX);
-  int wg = (chunks + 3) / 4;
-  return wg < LOSS_WG_PER_SAMPLE ? wg : LOSS_WG_PER_SAMPLE;
-}
 static inline int loss_rows(int HW) { return loss_blocks(HW); }
 
 extern "C" size_t dl_icp_loss_workspace_bytes(int32_t B, int32_t H, int32_t W) {
@@ -54,14 +46,6 @@ struct LossOut {
   float* grad_terms;
   uint32_t flags;
 };
-
-// Packed fp32: the kernel is bound by VALU issue once its operands sit in the infinity cache (which they do right after
-// the correspondence search), so two pixels travel through every arithmetic instruction (v_pk_fma_f32 / v_pk_mul_f32 /
-// v_pk_add_f32 on the register pairs the 16-byte loads deliver) and the accumulators hold even/odd-pixel partial sums.
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f2 fma2(float a, f2 b, f2 c) { return __builtin_elementwise_fma((f2){a, a}, b, c); }
-__device__ __forceinline__ f2 mul2(float a, f2 b) { return (f2){a, a} * b; }
 
 // Two matched pairs, branch-free: `w` (0 or 1 per pixel) masks pairs that do not count, so that the loads of several
 // pixels can be issued before any of them is consumed.  Per pixel the arithmetic is the same sequence of fp32
@@ -76,55 +60,48 @@ __device__ __forceinline__ void accumulate_pair2(f2 (&acc)[NA], const float (&m)
   const bool ht1 = (tnx.y != 0.f) || (tny.y != 0.f) || (tnz.y != 0.f);
   // po2po_alone (:36-45): no pair takes part in the normal-based terms, every matched source point in point-to-point
   const f2 w = {(valid0 && hs0 && ht0 && !alone) ? 1.f : 0.f, (valid1 && hs1 && ht1 && !alone) ? 1.f : 0.f};   // :110-121
-  const f2 qx = fma2(m[2], z, fma2(m[1], y, mul2(m[0], x))) + m[3];
-  const f2 qy = fma2(m[6], z, fma2(m[5], y, mul2(m[4], x))) + m[7];
-  const f2 qz = fma2(m[10], z, fma2(m[9], y, mul2(m[8], x))) + m[11];
+  const f2 qx = pk_fma(m[2], z, pk_fma(m[1], y, pk_mul(m[0], x))) + m[3];
+  const f2 qy = pk_fma(m[6], z, pk_fma(m[5], y, pk_mul(m[4], x))) + m[7];
+  const f2 qz = pk_fma(m[10], z, pk_fma(m[9], y, pk_mul(m[8], x))) + m[11];
   const f2 dx = qx - tx, dy = qy - ty, dz = qz - tz;
   {
     // point-to-plane (:196-203)
-    const f2 r = w * fma2(dz, tnz, fma2(dy, tny, dx * tnx));
-    acc[0] = fma2(r, r, acc[0]);
+    const f2 r = w * pk_fma(dz, tnz, pk_fma(dy, tny, dx * tnx));
+    acc[0] = pk_fma(r, r, acc[0]);
     const f2 gx = r * tnx, gy = r * tny, gz = r * tnz;
     acc[1] += gx; acc[2] += gy; acc[3] += gz;
-    acc[4] = fma2(gx, x, acc[4]); acc[5] = fma2(gx, y, acc[5]); acc[6] = fma2(gx, z, acc[6]);
-    acc[7] = fma2(gy, x, acc[7]); acc[8] = fma2(gy, y, acc[8]); acc[9] = fma2(gy, z, acc[9]);
-    acc[10] = fma2(gz, x, acc[10]); acc[11] = fma2(gz, y, acc[11]); acc[12] = fma2(gz, z, acc[12]);
+    acc[4] = pk_fma(gx, x, acc[4]); acc[5] = pk_fma(gx, y, acc[5]); acc[6] = pk_fma(gx, z, acc[6]);
+    acc[7] = pk_fma(gy, x, acc[7]); acc[8] = pk_fma(gy, y, acc[8]); acc[9] = pk_fma(gy, z, acc[9]);
+    acc[10] = pk_fma(gz, x, acc[10]); acc[11] = pk_fma(gz, y, acc[11]); acc[12] = pk_fma(gz, z, acc[12]);
     // plane-to-plane (:224-238) on the rotated source normal (deployer.py:297-299)
-    const f2 rx = fma2(m[2], nz, fma2(m[1], ny, mul2(m[0], nx)));
-    const f2 ry = fma2(m[6], nz, fma2(m[5], ny, mul2(m[4], nx)));
-    const f2 rz = fma2(m[10], nz, fma2(m[9], ny, mul2(m[8], nx)));
+    const f2 rx = pk_fma(m[2], nz, pk_fma(m[1], ny, pk_mul(m[0], nx)));
+    const f2 ry = pk_fma(m[6], nz, pk_fma(m[5], ny, pk_mul(m[4], nx)));
+    const f2 rz = pk_fma(m[10], nz, pk_fma(m[9], ny, pk_mul(m[8], nx)));
     f2 ex, ey, ez;
     if (LINEAR) {
-      const f2 c1 = w * (1.f - fma2(rz, tnz, fma2(ry, tny, rx * tnx)));
-      acc[13] = fma2(c1, c1, acc[13]);
+      const f2 c1 = w * (1.f - pk_fma(rz, tnz, pk_fma(ry, tny, rx * tnx)));
+      acc[13] = pk_fma(c1, c1, acc[13]);
       ex = -c1 * tnx; ey = -c1 * tny; ez = -c1 * tnz;
     } else {
       ex = w * (rx - tnx); ey = w * (ry - tny); ez = w * (rz - tnz);
-      acc[13] += fma2(ez, ez, fma2(ey, ey, ex * ex));
+      acc[13] += pk_fma(ez, ez, pk_fma(ey, ey, ex * ex));
     }
-    acc[14] = fma2(ex, nx, acc[14]); acc[15] = fma2(ex, ny, acc[15]); acc[16] = fma2(ex, nz, acc[16]);
-    acc[17] = fma2(ey, nx, acc[17]); acc[18] = fma2(ey, ny, acc[18]); acc[19] = fma2(ey, nz, acc[19]);
-    acc[20] = fma2(ez, nx, acc[20]); acc[21] = fma2(ez, ny, acc[21]); acc[22] = fma2(ez, nz, acc[22]);
+    acc[14] = pk_fma(ex, nx, acc[14]); acc[15] = pk_fma(ex, ny, acc[15]); acc[16] = pk_fma(ex, nz, acc[16]);
+    acc[17] = pk_fma(ey, nx, acc[17]); acc[18] = pk_fma(ey, ny, acc[18]); acc[19] = pk_fma(ey, nz, acc[19]);
+    acc[20] = pk_fma(ez, nx, acc[20]); acc[21] = pk_fma(ez, ny, acc[21]); acc[22] = pk_fma(ez, nz, acc[22]);
     acc[23] += w;
   }
   if (P2P) {
     // point-to-point on pairs without normals on either side (:85-100, :168-172)
     const f2 w2 = {(valid0 && (alone || (!hs0 && !ht0))) ? 1.f : 0.f, (valid1 && (alone || (!hs1 && !ht1))) ? 1.f : 0.f};
     const f2 ux = w2 * dx, uy = w2 * dy, uz = w2 * dz;
-    acc[ACC_N + 0] += fma2(uz, uz, fma2(uy, uy, ux * ux));
+    acc[ACC_N + 0] += pk_fma(uz, uz, pk_fma(uy, uy, ux * ux));
     acc[ACC_N + 1] += ux; acc[ACC_N + 2] += uy; acc[ACC_N + 3] += uz;
-    acc[ACC_N + 4] = fma2(ux, x, acc[ACC_N + 4]); acc[ACC_N + 5] = fma2(ux, y, acc[ACC_N + 5]); acc[ACC_N + 6] = fma2(ux, z, acc[ACC_N + 6]);
-    acc[ACC_N + 7] = fma2(uy, x, acc[ACC_N + 7]); acc[ACC_N + 8] = fma2(uy, y, acc[ACC_N + 8]); acc[ACC_N + 9] = fma2(uy, z, acc[ACC_N + 9]);
-    acc[ACC_N + 10] = fma2(uz, x, acc[ACC_N + 10]); acc[ACC_N + 11] = fma2(uz, y, acc[ACC_N + 11]); acc[ACC_N + 12] = fma2(uz, z, acc[ACC_N + 12]);
+    acc[ACC_N + 4] = pk_fma(ux, x, acc[ACC_N + 4]); acc[ACC_N + 5] = pk_fma(ux, y, acc[ACC_N + 5]); acc[ACC_N + 6] = pk_fma(ux, z, acc[ACC_N + 6]);
+    acc[ACC_N + 7] = pk_fma(uy, x, acc[ACC_N + 7]); acc[ACC_N + 8] = pk_fma(uy, y, acc[ACC_N + 8]); acc[ACC_N + 9] = pk_fma(uy, z, acc[ACC_N + 9]);
+    acc[ACC_N + 10] = pk_fma(uz, x, acc[ACC_N + 10]); acc[ACC_N + 11] = pk_fma(uz, y, acc[ACC_N + 11]); acc[ACC_N + 12] = pk_fma(uz, z, acc[ACC_N + 12]);
     acc[ACC_N + 13] += w2;
   }
-}
-
-// A value of another lane of the same 16-lane DPP row (CTRL: quad_perm 0x00-0xFF, row_ror:n 0x120+n, ...): a VALU
-// operand modifier -- no LDS traffic, unlike the ds_bpermute behind __shfl_xor.
-template <int CTRL>
-__device__ __forceinline__ float dpp_get(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
 
 // Sum of the partial rows of one sample in fp64 (fixed order) and the final means / gradient moments.  Runs in the
@@ -178,40 +155,6 @@ __device__ __forceinline__ void finalize_sample(const float* __restrict__ rows, 
     g[1 * 12 + t] = (out.flags & DL_LOSS_POINT_TO_PLANE) ? (float)(2.0 * po2pl / K) : 0.f;
     g[2 * 12 + t] = (out.flags & DL_LOSS_PLANE_TO_PLANE) ? (float)(2.0 * pl2pl / K) : 0.f;
   }
-}
-
-// Streamed operands of one 256-pixel chunk as a wave loads them: lane l holds pixels 4l..4l+3 of every plane.
-struct StreamRegs {
-  int4 j;                       // correspondence (validity)
-  float4 x, y, z, a, b, c;      // source point and normal
-  float4 tx, ty, tz, ta, tb, tc; // matched target point and normal
-};
-
-__device__ __forceinline__ StreamRegs load_stream(const int32_t* __restrict__ nn, const float* __restrict__ sp,
-                                                  const float* __restrict__ sn, const float* __restrict__ mt, int q4,
-                                                  int g4) {
-  StreamRegs r;
-  // Non-temporal hint on the thirteen streams (round 6): every byte is read once per launch, and with it a launch behind clean caches
-  // takes 13.2 us instead of 13.9 (0.50-0.51 of 8 TB/s instead of 0.48; with the operands in the infinity cache nothing changes).
-  typedef float nt_f4 __attribute__((ext_vector_type(4)));
-  typedef int nt_i4 __attribute__((ext_vector_type(4)));
-  auto ld4 = [](const float* p, int i) { const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(p) + i); return make_float4(v.x, v.y, v.z, v.w); };
-#define LD4(P, I) ld4(P, I)
-  { const nt_i4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_i4*>(nn) + g4); r.j = make_int4(v.x, v.y, v.z, v.w); }
-  r.x = LD4(sp, g4);
-  r.y = LD4(sp, q4 + g4);
-  r.z = LD4(sp, 2 * q4 + g4);
-  r.a = LD4(sn, g4);
-  r.b = LD4(sn, q4 + g4);
-  r.c = LD4(sn, 2 * q4 + g4);
-  r.tx = LD4(mt, g4);
-  r.ty = LD4(mt, q4 + g4);
-  r.tz = LD4(mt, 2 * q4 + g4);
-  r.ta = LD4(mt, 3 * q4 + g4);
-  r.tb = LD4(mt, 4 * q4 + g4);
-  r.tc = LD4(mt, 5 * q4 + g4);
-#undef LD4
-  return r;
 }
 
 // A pure streaming pass: thirteen fp32 planes per sample -- the correspondence map (validity), the source point and
@@ -271,47 +214,9 @@ __global__ __launch_bounds__(DL_BLOCK) void k_icp_loss(
       }
     }
   }
-  // Reduction over the workgroup.  Even/odd pixels first; then the four lanes of every quad TRANSPOSE-reduce the NA values
-  // (each butterfly step halves the number of values a lane carries: lane l of a quad ends up with the quad sums of
-  // accumulators 4k + l), two row rotations add the four quads of a 16-lane DPP row, and the 16 row sums of the workgroup
-  // meet in LDS where they are added in a fixed order: one partial row per workgroup.  ~70 VALU instructions for 24
-  // values instead of the 144 adds + 144 ds_bpermute of a shuffle tree per value, and no LDS traffic in the wave part.
-  constexpr int ROWS = DL_BLOCK / 16;
-  constexpr int NP = (NA + 3) / 4 * 4;
-  __shared__ float red[ROWS * ACC_PITCH];
-  float v[NP];
-#pragma unroll
-  for (int i = 0; i < NP; ++i) v[i] = i < NA ? acc[i].x + acc[i].y : 0.f;
-  const bool b0 = lane & 1, b1 = lane & 2;
-  float u[NP / 2];
-#pragma unroll
-  for (int k = 0; k < NP / 2; ++k) {
-    const float keep = b0 ? v[2 * k + 1] : v[2 * k], send = b0 ? v[2 * k] : v[2 * k + 1];
-    u[k] = keep + dpp_get<0xB1>(send);                  // quad_perm [1,0,3,2]: lane ^ 1
-  }
-  float q[NP / 4];
-#pragma unroll
-  for (int k = 0; k < NP / 4; ++k) {
-    const float keep = b1 ? u[2 * k + 1] : u[2 * k], send = b1 ? u[2 * k] : u[2 * k + 1];
-    q[k] = keep + dpp_get<0x4E>(send);                  // quad_perm [2,3,0,1]: lane ^ 2
-    q[k] += dpp_get<0x124>(q[k]);                       // row_ror:4
-    q[k] += dpp_get<0x128>(q[k]);                       // row_ror:8
-  }
-  if ((lane & 12) == 0) {                               // the first quad of every row holds the row's NA sums
-    float* dst = red + (threadIdx.x >> 4) * ACC_PITCH + (lane & 3);
-#pragma unroll
-    for (int k = 0; k < NP / 4; ++k) dst[4 * k] = q[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < ACC_PITCH) {
-    const int t = threadIdx.x;
-    float v = 0.f;
-    if (t < NA) {
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) v += red[r * ACC_PITCH + t];
-    }
-    partials[((size_t)b * gridDim.x + blockIdx.x) * ACC_PITCH + t] = v;
-  }
+  // one reduction (icp_stream.h) and one partial row per workgroup
+  __shared__ float red[(DL_BLOCK / 16) * ACC_PITCH];
+  wg_reduce_row<NA, ACC_PITCH>(acc, red, partials + ((size_t)b * gridDim.x + blockIdx.x) * ACC_PITCH);
 }
 
 // Measurement aid: the same thirteen 16-byte load streams as k_icp_loss with the arithmetic replaced by one add per

@@ -200,9 +200,14 @@ class NativeOdometry(object):
     arrives) and the three outputs.  ``push(points [3,N])`` returns None for the first scan, then (translation [1,3], quaternion [1,4],
     T [1,4,4]) -- tensors that the next push overwrites.  ``image_t_1`` / ``image_t`` are the images of the last pair.
     ``push_records(records, layout)`` is the same from raw point records (``dl_odometry_push_records``); the two may be mixed.
-    ``dtype``: as ``NativePoseNet`` (``torch.bfloat16`` / ``torch.float16``: ``dl_odometry_push_h`` / ``dl_odometry_push_records_h``)."""
+    ``dtype``: as ``NativePoseNet`` (``torch.bfloat16`` / ``torch.float16``: ``dl_odometry_push_h`` / ``dl_odometry_push_records_h``).
+    ``quality``: every push is followed by ``dl_odometry_quality`` with ``normal_params`` = (half_rows, half_cols, epsilon_range,
+    min_neighbors), what ``NormalsComputer._params`` returns: the object owns the two ``dl_scan_geometry`` records beside the two
+    images, and from the second scan on ``quality_out`` holds float64 device tensors ``information [6,6]``, ``rhs [6]``, ``stats [2]``
+    (sum of squared residuals, pairs), ``covariance [6,6]`` and ``status [1]`` int32 of the last pair.  The first push fills the record
+    of its image only.  The poses do not change by a bit."""
 
-    def __init__(self, model, sensor, max_points=1 << 17, dtype=torch.float32):
+    def __init__(self, model, sensor, max_points=1 << 17, dtype=torch.float32, quality=False, normal_params=None):
         self.pose = NativePoseNet(model, 1, sensor.H, sensor.W, own_workspace=False, dtype=dtype)     # (the forward's workspace is the head of this one's)
         self._h = self.pose._h
         self.lib, self.sensor, dev = self.pose.lib, sensor, self.pose.device
@@ -216,6 +221,35 @@ class NativeOdometry(object):
         self.cur, self.count = 0, 0
         # push_records from the host: two alternating page-locked staging buffers with the event behind their last transfer, one device buffer
         self._stage, self._stage_np, self._stage_event, self._stage_next, self._records = [None, None], [None, None], [None, None], 0, None
+        self.quality, self.quality_out = bool(quality), None
+        if self.quality:
+            if normal_params is None or len(normal_params) != 4:
+                raise ValueError("NativeOdometry(quality=True) needs normal_params = (half_rows, half_cols, epsilon_range, min_neighbors)")
+            self.normal_params = (int(normal_params[0]), int(normal_params[1]), float(normal_params[2]), int(normal_params[3]))
+            H, W = sensor.H, sensor.W
+            self.normals = torch.zeros((2, 3, H, W), dtype=torch.float32, device=dev)
+            self.packed_images = torch.zeros((2, H, W, 4), dtype=torch.float32, device=dev)
+            self.packed_normals = torch.zeros((2, H, W, 4), dtype=torch.float32, device=dev)
+            self._records_geometry = [_lib.ScanGeometry(self.normals[i].data_ptr(), self.packed_images[i].data_ptr(), self.packed_normals[i].data_ptr())
+                                      for i in range(2)]
+            nbytes = int(self.lib.dl_odometry_quality_workspace_bytes(ctypes.byref(sensor.struct), H, W))
+            if not nbytes:
+                raise _lib.DeloraHipError(f"dl_odometry_quality_workspace_bytes: {(self.lib.dl_last_error() or b'').decode()}")
+            self.quality_workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            self._quality_buffers = {"information": torch.zeros((6, 6), dtype=torch.float64, device=dev), "rhs": torch.zeros((6,), dtype=torch.float64, device=dev),
+                                     "stats": torch.zeros((2,), dtype=torch.float64, device=dev), "covariance": torch.zeros((6, 6), dtype=torch.float64, device=dev),
+                                     "status": torch.zeros((1,), dtype=torch.int32, device=dev)}
+
+    def _quality(self, prev):
+        """``dl_odometry_quality`` on the pair the push has just served (``prev`` None: the first scan, the record alone)."""
+        p, q = ring_conv._ptr, self._quality_buffers
+        a, b, eps, min_n = self.normal_params
+        geometry_prev = ctypes.byref(self._records_geometry[1 - self.cur]) if prev is not None else None
+        _lib.check(self.lib.dl_odometry_quality(ctypes.byref(self.sensor.struct), p(prev), geometry_prev, p(self.images[self.cur]),
+                                                ctypes.byref(self._records_geometry[self.cur]), p(self.T), a, b, eps, min_n, p(self.quality_workspace),
+                                                p(q["information"]), p(q["rhs"]), p(q["stats"]), p(q["covariance"]), p(q["status"]),
+                                                ring_conv._stream()), "dl_odometry_quality")
+        self.quality_out = q if prev is not None else None
 
     def _reserve(self, n_points):
         if self.workspace is not None and n_points <= self.max_points:
@@ -248,6 +282,8 @@ class NativeOdometry(object):
         _lib.check(getattr(self.lib, fn)(self.pose._net_p, p(self.pose.prepared), ctypes.byref(self.sensor.struct), p(points), points.stride(0), n,
                                          p(self.offs), p(prev), p(self.images[self.cur]), *self._h[1], p(self.workspace), p(self.translation),
                                          p(self.quaternion), p(self.T), ring_conv._stream()), fn)
+        if self.quality:
+            self._quality(prev)
         self.count += 1
         return (self.translation, self.quaternion, self.T) if prev is not None else None
 
@@ -303,6 +339,8 @@ class NativeOdometry(object):
         _lib.check(getattr(self.lib, fn)(self.pose._net_p, p(self.pose.prepared), ctypes.byref(self.sensor.struct), p(buf),
                                          nbytes // layout.point_step, ctypes.byref(layout), p(self.offs), p(prev), p(self.images[self.cur]),
                                          *self._h[1], p(self.workspace), p(self.translation), p(self.quaternion), p(self.T), ring_conv._stream()), fn)
+        if self.quality:
+            self._quality(prev)
         self.count += 1
         return (self.translation, self.quaternion, self.T) if prev is not None else None
 

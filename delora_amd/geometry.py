@@ -332,6 +332,38 @@ def icp_loss(T, src_image4, src_normals, match, nn_pix, flags):
     return _IcpLoss.apply(T, src_image4, src_normals, match, nn_pix, flags)
 
 
+def icp_information(T, src_image4, src_normals, match, nn_pix, workspace=None):
+    """Point-to-plane normal equations of the matched pairs at the pose ``T [B,4,4]`` (``dl_icp_information``): the operands of
+    ``icp_loss``.  Returns a dict of float64 tensors: ``information [B,6,6]`` = sum J J^T and ``rhs [B,6]`` = sum J r with
+    J = (n, q x n) -- a left perturbation, translation first --, ``sum_r2 [B]``, ``pairs [B]``, ``covariance [B,6,6]`` =
+    sum_r2 / (pairs - 6) * information^-1 (zeros unless status is 0) and ``status [B]`` int32 (``_lib.INFO_*``).  Nothing is refined:
+    T is only read.  ``workspace``: an optional caller-owned fp32 device tensor of ``dl_icp_information_workspace_bytes`` bytes."""
+    lib = _lib.load()
+    _require_cuda(T, src_image4, src_normals, match, nn_pix)
+    s, s_ss = _planar(src_image4, 3)
+    sn, sn_ss = _planar(src_normals, 3)
+    mt, mt_ss = _planar(match, 6)
+    if nn_pix.dtype != torch.int32 or not nn_pix.is_contiguous():
+        raise ValueError("nn_pix must be a contiguous int32 [B,H,W] tensor")
+    B, _, H, W = s.shape
+    dev = s.device
+    Tc = T.detach().contiguous().float()
+    info = torch.empty((B, 6, 6), dtype=torch.float64, device=dev)
+    rhs = torch.empty((B, 6), dtype=torch.float64, device=dev)
+    stats = torch.empty((B, 2), dtype=torch.float64, device=dev)
+    cov = torch.empty((B, 6, 6), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    need = int(lib.dl_icp_information_workspace_bytes(B, H, W))
+    if not need:
+        raise _lib.DeloraHipError((lib.dl_last_error() or b"").decode())
+    ws = workspace if workspace is not None else torch.empty((need // 4,), dtype=torch.float32, device=dev)
+    if ws.numel() * ws.element_size() < need or not ws.is_contiguous():
+        raise ValueError(f"workspace needs {need} contiguous bytes")
+    _lib.check(lib.dl_icp_information(_ptr(s), s_ss, _ptr(sn), sn_ss, _ptr(mt), mt_ss, _ptr(nn_pix), _ptr(Tc), B, H, W, _ptr(info), _ptr(rhs),
+                                      _ptr(stats), _ptr(cov), _ptr(status), _ptr(ws), _stream()), "dl_icp_information")
+    return {"information": info, "rhs": rhs, "sum_r2": stats[:, 0], "pairs": stats[:, 1], "covariance": cov, "status": status}
+
+
 def loss_flags(config):
     """Flag word of dl_icp_loss_fwd from the reference's hyper-parameters (config/hyperparameters.yaml:14-19).
 

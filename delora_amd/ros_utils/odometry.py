@@ -19,6 +19,7 @@ import torch
 from .. import _lib, geometry
 from ..models import model as model_module
 from ..models import model_parts
+from ..preprocessing.normal_computation import NormalsComputer
 
 
 def quaternion_from_matrix(matrix):
@@ -139,13 +140,29 @@ class ScanToScanOdometry(object):
     binds the half-precision family (``NativeOdometry(dtype=...)``: every trunk weight converted once).  ``config["amp_dtype"]`` is
     deliberately NOT read: a caller who passes a training config gets fp32, as ever.  ``config["amp_stem"]`` IS followed by engine
     "torch" in half precision (the model is built from the config: conv1 then runs on rounded operands as in training); engine "native"
-    keeps conv1 in fp32 whatever the key says."""
+    keeps conv1 in fp32 whatever the key says.
+
+    ``quality=True``: every result dict gains how well the pair constrains the returned motion, from the point-to-plane normal equations
+    of the matched pairs at that motion (``geometry.icp_information``; nothing is refined, the pose is the network's):
+    ``covariance`` [6,6] float64, row-major (x, y, z, rot X, rot Y, rot Z) -- the layout of ``nav_msgs/Odometry.pose.covariance`` --, the
+    covariance of the scan-to-scan transform under a left perturbation, in the previous scan's frame (zeros unless ``quality_status`` is
+    0, which is what the reference publishes); ``information`` [6,6]; ``residual_rms`` = sqrt(sum r^2 / pairs); ``pairs``;
+    ``quality_status`` (0 fine, 1 at most six pairs, 2 unobservable along some axis); ``information_eigenvalues`` [6], ascending, of the
+    information matrix scaled to a unit diagonal (NaN where a diagonal entry is not positive).  Engine "torch" chains
+    ``geometry.normals`` (both images, one launch), ``geometry.nn_correspond`` and ``geometry.icp_information``; engine "native" calls
+    ``dl_odometry_quality`` -- the same kernels on the same operands.  The normal parameters are ``NormalsComputer._params`` of the config.
+    Not served together with ``normalization_scaling`` (the clouds are rescaled per pair).  Propagating the covariance into the
+    integrated pose ``T_0_t`` is left to the caller.  ``quality=False`` (default): today's keys, nothing new is launched."""
 
     PRECISIONS = {"float32": torch.float32, "bfloat16": torch.bfloat16, "float16": torch.float16}
 
-    def __init__(self, config, model=None, project_pair=None, engine="torch", precision="float32"):
+    def __init__(self, config, model=None, project_pair=None, engine="torch", precision="float32", quality=False):
         if engine not in ("torch", "native"):
             raise ValueError(f"engine must be 'torch' or 'native', got {engine!r}")
+        self.quality = bool(quality)
+        if self.quality and config["normalization_scaling"]:
+            raise ValueError("quality=True does not serve normalization_scaling: it rescales both clouds per pair, so the covariance would "
+                             "not be in metres and the previous scan's normals could not be reused")
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be 'float32', 'bfloat16' or 'float16', got {precision!r}")
         self.precision, self.dtype = precision, self.PRECISIONS[precision]
@@ -154,6 +171,7 @@ class ScanToScanOdometry(object):
         self.device = config["device"]
         self.dataset = config["datasets"][0]                       # "Assumes the dataset in config['datasets'][0]" (:26)
         self.sensor = geometry.Sensor.from_config(config, self.dataset)
+        self.normal_params = NormalsComputer(config, self.dataset)._params() if self.quality else None
         if model is None:
             model = model_module.OdometryModel(config=config).to(self.device)
             if config.get("checkpoint"):
@@ -178,7 +196,31 @@ class ScanToScanOdometry(object):
             why = native_infer.why_unsupported(self.model, self.sensor.H, self.sensor.W)
             if why is not None:
                 raise ValueError("engine 'native': " + why)
-            self.native = native_infer.NativeOdometry(self.model, self.sensor, dtype=self.dtype)
+            self.native = native_infer.NativeOdometry(self.model, self.sensor, dtype=self.dtype, quality=self.quality, normal_params=self.normal_params)
+
+    @staticmethod
+    def _quality_result(information, sum_r2, pairs, covariance, status):
+        """The quality keys of a result dict from the device outputs of one sample."""
+        info = information.cpu().numpy().astype(np.float64).reshape(6, 6)
+        sum_r2, pairs = float(sum_r2), float(pairs)
+        d = np.diag(info)
+        if np.all(np.isfinite(info)) and np.all(d > 0):
+            s = 1.0 / np.sqrt(d)
+            eig = np.linalg.eigvalsh((info * s[:, None]) * s[None, :])
+        else:
+            eig = np.full((6,), np.nan)
+        return {"covariance": covariance.cpu().numpy().astype(np.float64).reshape(6, 6), "information": info,
+                "residual_rms": math.sqrt(sum_r2 / pairs) if pairs > 0 and sum_r2 >= 0 else float("nan"), "pairs": int(pairs),
+                "quality_status": int(status), "information_eigenvalues": eig}
+
+    def _native_result(self, out):
+        if out is None:
+            return None
+        result = self._result(out[2], out[0])
+        if self.quality:
+            q = self.native.quality_out
+            result.update(self._quality_result(q["information"], q["stats"][0], q["stats"][1], q["covariance"], q["status"][0]))
+        return result
 
     def _result(self, T, translation_1):
         """The returned dict from ``T [1,4,4]`` and ``translation [1,3]`` (odometry_publisher.py:151-172)."""
@@ -210,8 +252,7 @@ class ScanToScanOdometry(object):
         current = scan[:, :3].to(self.device).float().clone()
         result = None
         if self.native is not None:
-            out = self.native.push(current[0].contiguous())          # (a filtered numpy scan arrives with transposed strides)
-            return None if out is None else self._result(out[2], out[0])
+            return self._native_result(self.native.push(current[0].contiguous()))     # (a filtered numpy scan arrives with transposed strides)
         if self.point_cloud_t_1 is not None:
             previous = self.point_cloud_t_1
             if self.config["normalization_scaling"]:
@@ -234,6 +275,14 @@ class ScanToScanOdometry(object):
             if self.integrator is not None:
                 gt, gq = self.integrator.update_transformation(quaternion=quaternion, translation=translation)
                 result.update(global_translation=gt, global_quaternion=gq, T_0_t=self.integrator.T_0_t[0].copy())
+            if self.quality:
+                # source = the current scan, target = the previous one: the direction of T
+                a, b, eps, min_n = self.normal_params
+                nrm, nrm_packed = geometry.normals(images, a, b, eps, min_n, want_packed=True)
+                nn_pix, _, match = geometry.nn_correspond(images[1:2], nrm[1:2], geometry.pack_image(images[0:1]), nrm_packed[0:1], T, self.sensor,
+                                                          need_without_normals=False, want_visible=False)
+                q = geometry.icp_information(T, images[1:2], nrm[1:2], match, nn_pix)
+                result.update(self._quality_result(q["information"][0], q["sum_r2"][0], q["pairs"][0], q["covariance"][0], q["status"][0]))
         self.point_cloud_t_1 = current * self.scaling_factor                    # undo the in-place scaling (:172)
         return result
 
@@ -257,6 +306,5 @@ class ScanToScanOdometry(object):
         if self.native is not None and message.flags.c_contiguous:
             from ..deploy import native_infer
             if native_infer.why_layout_unsupported(layout) is None:
-                out = self.native.push_records(message, layout)
-                return None if out is None else self._result(out[2], out[0])
+                return self._native_result(self.native.push_records(message, layout))
         return self.push(unpack_records(message, layout))

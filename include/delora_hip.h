@@ -337,6 +337,52 @@ int dl_icp_loss_bwd(const float* grad_terms, const float* grad_loss_terms, int32
                     dl_stream stream);
 
 /*
+ * Point-to-plane normal equations of the matched pairs (csrc/info.hip; additive, ABI 10 as it stands): how well the pairs constrain
+ * the pose T, as an information matrix and a covariance.  The reference's node publishes a nav_msgs/Odometry whose 6x6
+ * pose.covariance it never sets (src/ros_utils/odometry_publisher.py:128-172); this is the quantity that belongs there.  It is NOT a
+ * refinement: no Gauss-Newton step is taken or returned.
+ * The inputs are exactly those of dl_icp_loss_fwd (thirteen planes streamed once, 52 B per source pixel).  Per source pixel, in fp32
+ * unless said otherwise:
+ *   q = fma(m2, z, fma(m1, y, m0 * x)) + m3 per row of T (the chain of dl_icp_loss_fwd and dl_reproject), used for the moment arm;
+ *   the residual, the one quantity that cancels (centimetres on coordinates of tens of metres near a converged pose), is formed in
+ *   FP64 from the fp32 operands and rounded ONCE to fp32:  d = (fma(m2, z, fma(m1, y, m0 * x)) + m3) - p_t per row,
+ *   r = (float) fma(dz, n_z, fma(dy, n_y, dx * n_x)) with n the MATCHED TARGET normal (match planes 3..5; it is not normalised
+ *   here) -- its error is relative to |r|, not to |q|; on small-integer data it is the value of the fp32 chain, bit for bit;
+ *   a = q x n:  a_x = fma(q_y, n_z, -(q_z * n_y)),  a_y = fma(q_z, n_x, -(q_x * n_z)),  a_z = fma(q_x, n_y, -(q_y * n_x)),
+ *   J = (n_x, n_y, n_z, a_x, a_y, a_z): the derivative of r under the LEFT perturbation q <- q + omega x q + v with respect to
+ *       (v, omega) -- translation first, the order of pose.covariance (x, y, z, rotation about X, Y, Z), in the TARGET frame,
+ *   w = 1 iff nn_pix >= 0, the source normal is not the zero vector and the matched normal is not the zero vector (the point-to-plane
+ *       pair set of dl_icp_loss_fwd), else 0.  Masking is multiplicative, with dl_icp_loss_fwd's contract: the operands of pixels that
+ *       do not count must be FINITE (then they contribute an exact zero), pixel 0 included where H*W is not a multiple of 256.
+ * Outputs per sample, all fp64 (the fp32 per-lane sums are added per workgroup in fp32 and across workgroups in fp64, fixed order):
+ *   info       [B][6][6]  sum w J J^T (the 21 unique sums are accumulated once, both triangles written)
+ *   rhs        [B][6]     sum w J r   (half the gradient of sum w r^2 under the perturbation)
+ *   stats      [B][2]     sum w r^2,  K = sum w
+ *   covariance [B][6][6]  sigma^2 info^-1 with sigma^2 = sum w r^2 / (K - 6) where status is DL_INFO_OK, else all +0.0 (what the
+ *                         reference publishes today)
+ *   status     [B] int32  DL_INFO_TOO_FEW_PAIRS if K <= 6; else DL_INFO_UNOBSERVABLE if a diagonal entry of info is not > 0 or, with
+ *                         D = diag(info) and Ah = D^-1/2 info D^-1/2 (Ah_ij = (info_ij * s_i) * s_j, s_i = 1 / sqrt(info_ii)), a
+ *                         pivot of the Cholesky factorisation of Ah -- the remainder Ah_jj - sum_c L_jc^2 before its square root -- is not
+ *                         > DL_INFO_MIN_PIVOT; else DL_INFO_OK.  The test is scale free (metres or millimetres, ten pairs or a million:
+ *                         Ah has a unit diagonal), and the constant is part of this contract.  "not >" makes a NaN -- a non-finite
+ *                         T[b] -- unobservable; such a pose stays in sample b, the other samples' outputs do not change by a bit.
+ *   workspace  dl_icp_information_workspace_bytes(B, H, W) bytes (host arithmetic: one row of 32 floats per workgroup), 16-byte aligned
+ * DL_ERR_INVALID_ARGUMENT before any launch, the text naming the entry point: a null pointer; B, H or W <= 0, H*W above 2^30 or
+ * B above 65535 (the size function then returns 0); a scan stride below the dense size (src_ss, srcn_ss >= 3*H*W, match_ss >= 6*H*W);
+ * where H*W is a multiple of 4, planes or strides that are not 16-byte aligned; a workspace that is not 16-byte aligned.
+ * Two launches on `stream`; no floating-point atomic, synchronisation, allocation or read-back: the same inputs give the same bits
+ * on every run, and the call is capturable into a HIP graph.  tests/information_ref.py is the plain float64 restatement.
+ */
+#define DL_INFO_OK 0
+#define DL_INFO_TOO_FEW_PAIRS 1
+#define DL_INFO_UNOBSERVABLE 2
+#define DL_INFO_MIN_PIVOT 1e-10
+size_t dl_icp_information_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int dl_icp_information(const float* src_image4, int64_t src_ss, const float* src_normals, int64_t srcn_ss, const float* match,
+                       int64_t match_ss, const int32_t* nn_pix, const float* T, int32_t B, int32_t H, int32_t W, double* info,
+                       double* rhs, double* stats, double* covariance, int32_t* status, void* workspace, dl_stream stream);
+
+/*
  * Exact nearest neighbour between two free-form point lists (no range-image structure), fp64
  * distances, LDS-tiled brute force.  Backs the list-based ICPLosses.forward signature
  * (src/losses/icp_losses.py:28-33) when the caller has lists rather than images.
@@ -1004,6 +1050,36 @@ int dl_odometry_push_records_h(const dl_pose_net* net, const void* prepared, con
                                int32_t n_records, const dl_record_layout* layout, int32_t* offs, const float* image_prev,
                                float* image_cur, int32_t dtype, void* workspace, float* translation, float* quaternion, float* T,
                                dl_stream stream);
+
+/*
+ * POSE QUALITY BEHIND A PUSH (csrc/info.hip; additive, ABI 10 as it stands): dl_odometry_quality is called after dl_odometry_push / _push_records
+ * (either family: it reads only the two fp32 images and T, never the network) and answers how well the pair constrains T.
+ * The library keeps no state: beside each of the two ping-pong images the caller owns one dl_scan_geometry record
+ *   normals [3][H][W] planar, packed_image [H][W][4] = (x, y, z, range), packed_normals [H][W][4] = (nx, ny, nz, 0), 16-byte aligned,
+ * swapped together with the images.  The call
+ *   1. fills the record of image_cur: dl_normals (S = 1) with the caller's half_rows, half_cols, epsilon_range, min_neighbors, and the
+ *      packed twin of the image (a bit copy);
+ *   2. when image_prev and geometry_prev (filled by the previous call) are given: dl_nn_correspond with source = current, target =
+ *      previous -- the direction of T in dl_odometry_push --, need_without_normals = 0, nn_pix and match in the workspace;
+ *   3. dl_icp_information with B = 1: info [6][6], rhs [6], stats [2], covariance [6][6] (fp64) and status [1] as documented there.
+ *      The covariance is that of the scan-to-scan transform T under a left perturbation, in the PREVIOUS scan's frame, row-major in
+ *      the order (x, y, z, rotation about X, Y, Z) of nav_msgs/Odometry's pose.covariance.
+ * image_prev == NULL (the first scan) only fills the record; T, workspace and the outputs may then be NULL and are not written.
+ *   workspace  dl_odometry_quality_workspace_bytes(sensor, H, W) bytes (H, W the sensor's; host arithmetic, 0 with a text for a refused
+ *              sensor), 256-byte aligned: nn_pix | match | the search's scratch | the partial rows.
+ * Null or misaligned pointers, a bad sensor and a window outside dl_normals' range are DL_ERR_INVALID_ARGUMENT before any launch.
+ * Nothing is allocated, nothing synchronises, the call is capturable.  normalization_scaling is not served, as in dl_odometry_push.
+ */
+typedef struct {
+  float* normals;          /* [3][H][W] */
+  float* packed_image;     /* [H][W][4] */
+  float* packed_normals;   /* [H][W][4] */
+} dl_scan_geometry;
+size_t dl_odometry_quality_workspace_bytes(const dl_sensor* sensor, int32_t H, int32_t W);
+int dl_odometry_quality(const dl_sensor* sensor, const float* image_prev, const dl_scan_geometry* geometry_prev, const float* image_cur,
+                        const dl_scan_geometry* geometry_cur, const float* T, int32_t half_rows, int32_t half_cols, float epsilon_range,
+                        int32_t min_neighbors, void* workspace, double* info, double* rhs, double* stats, double* covariance,
+                        int32_t* status, dl_stream stream);
 
 /*
  * What the convolution dispatch would launch (for tests and tools; host only, nothing is enqueued): runs the matching entry point's

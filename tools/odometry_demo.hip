@@ -3,7 +3,8 @@
 // as INTEGRATION.md section C describes for a C or C++ caller.  The counterpart of the reference's inference node (bin/run_rosnode.py)
 // without ROS.
 //
-//   odometry_demo [--half bf16|f16] [--records <point_step> <off_x> <off_y> <off_z>] <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...
+//   odometry_demo [--half bf16|f16] [--records <point_step> <off_x> <off_y> <off_z>] [--quality <half_rows> <half_cols> <epsilon_range> <min_neighbors>]
+//                 <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...
 //
 // With --half the same program runs through the half-precision family (dl_pose_net_prepare_h, dl_odometry_push_h /
 // dl_odometry_push_records_h): the fp32 weight file is converted once by the prepare call, the trunk runs in bf16 / fp16.
@@ -12,6 +13,12 @@
 // point_step-byte records; a KITTI .bin file is --records 16 0 4 8): they are uploaded as they are and pushed through
 // dl_odometry_push_records with the reference node's filter (exactly-zero coordinates and ranges within 0.3 m are dropped inside
 // the projection) -- nothing is filtered, compacted or transposed on the host.
+//
+// With --quality every push is followed by dl_odometry_quality with the given normal-estimation window (the shipped config is
+// --quality 3 5 0.5 10): the program owns the two dl_scan_geometry records beside its two images, and every line ends with
+//   quality <status> pairs <K> cov_diag <6 numbers>
+// the status (0 fine, 1 at most six pairs, 2 unobservable), the pair count and the diagonal of the 6x6 covariance of the scan-to-scan
+// transform (x, y, z, rotation about X, Y, Z; zeros unless the status is 0), which is also printed per push.
 //
 // One line per pair of consecutive scans:   <index> T <16 x 8 hex digits> pose <12 numbers>
 // T = the fp32 bit patterns of the row-major 4x4 transform (previous -> current), pose = the first three rows of the accumulated
@@ -38,6 +45,9 @@
 #include "../delora_amd/csrc/heads.hip"
 #include "../delora_amd/csrc/convh.hip"
 #include "../delora_amd/csrc/infer.hip"
+#include "../delora_amd/csrc/normals.hip"
+#include "../delora_amd/csrc/nn.hip"
+#include "../delora_amd/csrc/info.hip"
 
 #define HIP_OK(call)                                                                                         \
   do {                                                                                                       \
@@ -183,9 +193,26 @@ int main(int argc, char** argv) {
     argc -= 5;
     argv += 5;
   }
+  // ---- the optional pose quality
+  bool quality = false;
+  int32_t half_rows = 0, half_cols = 0, min_neighbors = 0;
+  float epsilon_range = 0.f;
+  if (argc > 1 && !strcmp(argv[1], "--quality")) {
+    if (argc < 6) die("--quality needs <half_rows> <half_cols> <epsilon_range> <min_neighbors>");
+    char* after[4] = {nullptr, nullptr, nullptr, nullptr};
+    half_rows = (int32_t)strtol(argv[2], &after[0], 10);
+    half_cols = (int32_t)strtol(argv[3], &after[1], 10);
+    epsilon_range = strtof(argv[4], &after[2]);
+    min_neighbors = (int32_t)strtol(argv[5], &after[3], 10);
+    for (int k = 0; k < 4; ++k)
+      if (after[k] == argv[2 + k] || *after[k]) die(std::string("--quality: not a number: ") + argv[2 + k]);
+    quality = true;
+    argc -= 5;
+    argv += 5;
+  }
   if (argc < 5)
-    die("usage: odometry_demo [--half bf16|f16] [--records <point_step> <off_x> <off_y> <off_z>] <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...   (scans: "
-        "float32 [3][N], or raw records with --records)");
+    die("usage: odometry_demo [--half bf16|f16] [--records <point_step> <off_x> <off_y> <off_z>] [--quality <half_rows> <half_cols> <epsilon_range> "
+        "<min_neighbors>] <weights.dlpose> <out.txt> <scan0.bin> <scan1.bin> ...   (scans: float32 [3][N], or raw records with --records)");
   const size_t unit = records ? (size_t)layout.point_step : 12;        // bytes per point in a scan file
   // ---- the weight file
   const std::vector<char> blob = read_file(argv[1]);
@@ -280,6 +307,22 @@ int main(int argc, char** argv) {
   HIP_OK(hipMalloc((void**)&d_pts, max_points ? max_points * unit : 256));
   HIP_OK(hipMalloc((void**)&d_offs, 256));
   HIP_OK(hipMalloc((void**)&d_out, 256));                              // translation [3] | quaternion [4] | T [16] at floats 0, 4, 8
+  // pose quality: one dl_scan_geometry record beside each image, the call's workspace and its outputs (doubles 0.. info [36] | rhs [6] |
+  // stats [2] | covariance [36], then the int32 status)
+  dl_scan_geometry records_geometry[2] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+  void* quality_ws = nullptr;
+  double* d_quality = nullptr;
+  if (quality) {
+    const size_t q_bytes = dl_odometry_quality_workspace_bytes(&sensor, H, W);
+    if (!q_bytes) die(std::string("dl_odometry_quality_workspace_bytes: ") + dl_last_error());
+    HIP_OK(hipMalloc(&quality_ws, q_bytes));
+    HIP_OK(hipMalloc((void**)&d_quality, 81 * sizeof(double)));
+    for (int k = 0; k < 2; ++k) {
+      HIP_OK(hipMalloc((void**)&records_geometry[k].normals, (size_t)3 * H * W * 4));
+      HIP_OK(hipMalloc((void**)&records_geometry[k].packed_image, (size_t)4 * H * W * 4));
+      HIP_OK(hipMalloc((void**)&records_geometry[k].packed_normals, (size_t)4 * H * W * 4));
+    }
+  }
   hipStream_t stream;
   HIP_OK(hipStreamCreate(&stream));
   if (half) DL_OK_OR_DIE(dl_pose_net_prepare_h(&net, 1, H, W, half, prepared, stream));
@@ -306,8 +349,14 @@ int main(int argc, char** argv) {
     else
       DL_OK_OR_DIE(dl_odometry_push(&net, prepared, &sensor, d_pts, (int64_t)n, (int32_t)n, d_offs, i ? images[1 - cur] : nullptr, images[cur], workspace,
                                     d_out, d_out + 4, d_out + 8, stream));
+    if (quality)                                                     // the records swap with the images
+      DL_OK_OR_DIE(dl_odometry_quality(&sensor, prev, i ? &records_geometry[1 - cur] : nullptr, images[cur], &records_geometry[cur], d_out + 8, half_rows,
+                                       half_cols, epsilon_range, min_neighbors, quality_ws, d_quality, d_quality + 36, d_quality + 42, d_quality + 44,
+                                       (int32_t*)(d_quality + 80), stream));
     float T[16];
+    double q_host[81];
     if (i) HIP_OK(hipMemcpyAsync(T, d_out + 8, sizeof(T), hipMemcpyDeviceToHost, stream));
+    if (i && quality) HIP_OK(hipMemcpyAsync(q_host, d_quality, sizeof(q_host), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));                            // (also: the scan buffer is free for the next copy)
     if (!i) continue;
     double next[4][4];
@@ -327,11 +376,25 @@ int main(int argc, char** argv) {
     fprintf(out, " pose");
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 4; ++c) fprintf(out, " %.9e", pose[r][c]);
+    if (quality) {
+      int32_t status;
+      memcpy(&status, &q_host[80], 4);
+      fprintf(out, " quality %d pairs %.0f cov_diag", status, q_host[43]);
+      printf("push %zu: status %d, %.0f pairs, covariance diagonal", i, status, q_host[43]);
+      for (int k = 0; k < 6; ++k) {
+        fprintf(out, " %.9e", q_host[44 + 7 * k]);
+        printf(" %.3e", q_host[44 + 7 * k]);
+      }
+      printf("\n");
+    }
     fprintf(out, "\n");
   }
   if (fclose(out)) die(std::string("cannot finish ") + argv[2]);
   HIP_OK(hipStreamDestroy(stream));
-  for (void* p : {(void*)d_weights, prepared, workspace, (void*)images[0], (void*)images[1], (void*)d_pts, (void*)d_offs, (void*)d_out}) HIP_OK(hipFree(p));
+  for (void* p : {(void*)d_weights, prepared, workspace, (void*)images[0], (void*)images[1], (void*)d_pts, (void*)d_offs, (void*)d_out, quality_ws,
+                  (void*)d_quality, (void*)records_geometry[0].normals, (void*)records_geometry[0].packed_image, (void*)records_geometry[0].packed_normals,
+                  (void*)records_geometry[1].normals, (void*)records_geometry[1].packed_image, (void*)records_geometry[1].packed_normals})
+    if (p) HIP_OK(hipFree(p));
   printf("odometry_demo: %zu scans, %zu poses -> %s\n", scans.size(), scans.empty() ? (size_t)0 : scans.size() - 1, argv[2]);
   return 0;
 }
