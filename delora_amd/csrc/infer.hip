@@ -2,6 +2,7 @@
 // (RingStem, RingSegment.forward) and model_parts.FusedHeads do per forward pass -- as a plan-and-forward family on the library's own
 // entry points, and the streaming scan -> pose call on top of it.  Nothing here computes: apart from the input interleave below every
 // launch is one of the existing entry points', called with the operands the Python path gives it, so the results are the same bits.
+#include <initializer_list>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -85,11 +86,31 @@ int pose_check(const char* who, const dl_pose_net* net, int B, int H, int W) {
     if (!q.p) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: heads.%s is null", who, q.name);
   return DL_OK;
 }
+// One trunk convolution.  The table of these records is the single statement of the layer walk: the plan sizes the workspace from it,
+// prepare fills the records' ranges of `prepared`, forward runs them in order.
+enum LayerKind { kWino, kDirect, kHalf };           // dl_wino_conv3x3_nhwc_f32, dl_conv2d_nhwc_f32, dl_conv2d_nhwc_h
+constexpr size_t kNone = ~(size_t)0;
+
+struct Layer {
+  LayerKind kind;
+  int block;                                        // error texts say blocks[block].name
+  const char* name;                                 // "w1", "wd", "w2"
+  const float* weight;                              // the fp32 parameter [cout][taps][cin]
+  int taps, cin, cout;
+  int h, w, sh, sw;                                 // input map and stride
+  int in, out, add;                                 // activation slots; add < 0: no addend
+  int act;
+  uint32_t epilogue;
+  size_t prepared;                                  // byte offset of the layer's weights in `prepared`; kNone: it reads the parameter
+};
 
 // Where everything lives.  Four rotating activation slots: the stem puts the interleaved input, conv1's output and the pooled map
 // into slots 0, 1, 2; a block whose input sits in slot s writes y1 to s+1, the shortcut to s+2 and y2 to s+3 (mod 4), and y2 is the
 // next block's input -- at no time more than those four tensors are alive.  A slot is as large as the largest tensor it ever holds.
 struct PosePlan {
+  Layer layers[3 * DL_POSE_NET_MAX_BLOCKS];         // in execution order: w1, wd, w2 per block
+  int n_layers;
+  int last_slot, last_hw;                           // the last block's output: its slot and its pixels per image
   size_t slot_bytes[4], slot_off[4];
   size_t win_off, split_off, feat_off, a1_off, a2_off, rot_off, norm_off, total;
   size_t split_bytes, prepared_bytes;
@@ -99,31 +120,49 @@ struct PosePlan {
 // the Python plan (ring_conv.wino_ok: C % 8 == 0, K % 64 == 0) holds for every such layer, and the launch itself refuses what it cannot run.
 inline bool runs_wino(int sh, int sw) { return sh == 1 && sw == 1; }
 
-PosePlan pose_plan(const dl_pose_net* net, int B, int H, int W) {
-  PosePlan p;
-  memset(&p, 0, sizeof(p));
-  auto hold = [&](int slot, size_t floats) { if (floats * 4 > p.slot_bytes[slot]) p.slot_bytes[slot] = floats * 4; };
-  auto split = [&](int h, int w, int c, int k) {
-    const size_t n = dl_wino_conv3x3_workspace_bytes(B, h, w, c, k);
-    if (n > p.split_bytes) p.split_bytes = n;
-    p.prepared_bytes += dl_wino_weights_floats(k, c) * sizeof(float);
+// The table and the sizes for a network pose_check has accepted.  dtype DL_DTYPE_F32: Winograd / direct layers, fp32 throughout, the
+// pooling's int8 window plane and the largest split-K scratch.  Half precision (ResNetModified.pooled_features_drop inside
+// torch.autocast): interleave and conv1 stay fp32 (slots 0 and 1), the pooled map and everything behind it has 2-byte elements, every
+// layer is dl_conv2d_nhwc_h (one kernel family: nothing to route), no window plane, no split-K scratch.
+// `prepared` offsets follow the header's layout, not the execution order: per block w1, w2, wd, those that have prepared weights --
+// fp32: the Winograd layers, dl_wino_weights_floats floats each, packed; half: every layer's w_fwd [taps][K][C], each rounded up to 256 bytes.
+PosePlan pose_plan(const dl_pose_net* net, int dtype, int B, int H, int W) {
+  PosePlan p{};
+  const bool half = dtype != DL_DTYPE_F32;
+  const size_t es = half ? 2 : 4;
+  auto hold = [&](int slot, size_t bytes) { if (bytes > p.slot_bytes[slot]) p.slot_bytes[slot] = bytes; };
+  auto layer = [&](int block, const char* name, const float* weight, int taps, int cin, int cout, int h, int w, int sh, int sw, int in, int out, int add,
+                   int act, uint32_t epilogue) {
+    const LayerKind kind = half ? kHalf : taps == 9 && runs_wino(sh, sw) ? kWino : kDirect;      // the one routing decision
+    Layer* l = &p.layers[p.n_layers++];
+    *l = Layer{kind, block, name, weight, taps, cin, cout, h, w, sh, sw, in, out, add, act, epilogue, kNone};
+    hold(out, (size_t)B * ceil_div(h, sh) * ceil_div(w, sw) * cout * es);
+    if (kind == kWino) {
+      const size_t n = dl_wino_conv3x3_workspace_bytes(B, h, w, cin, cout);
+      if (n > p.split_bytes) p.split_bytes = n;
+    }
+    return l;
   };
-  hold(0, (size_t)B * H * W * 8);
-  hold(1, (size_t)B * H * (W / 2) * 64);
-  hold(2, (size_t)B * H * (W / 4) * 64);
-  const size_t win_bytes = (size_t)B * H * (W / 4) * 64;
+  hold(0, (size_t)B * H * W * 8 * 4);
+  hold(1, (size_t)B * H * (W / 2) * 64 * 4);
+  hold(2, (size_t)B * H * (W / 4) * 64 * es);
+  const size_t win_bytes = half ? 0 : (size_t)B * H * (W / 4) * 64;
   int s = 2, h = H, w = W / 4;
   for (int i = 0; i < net->n_blocks; ++i) {
     const dl_pose_block& b = net->blocks[i];
+    const int y1 = (s + 1) & 3, sc = (s + 2) & 3, y2 = (s + 3) & 3;
     const int ho = ceil_div(h, b.stride_h), wo = ceil_div(w, b.stride_w);
-    const size_t out = (size_t)B * ho * wo * b.cout;
-    hold((s + 1) & 3, out);
-    if (b.has_downsample) hold((s + 2) & 3, out);
-    hold((s + 3) & 3, out);
-    if (runs_wino(b.stride_h, b.stride_w)) split(h, w, b.cin, b.cout);
-    split(ho, wo, b.cout, b.cout);
-    s = (s + 3) & 3; h = ho; w = wo;
+    Layer* const l1 = layer(i, "w1", b.w1, 9, b.cin, b.cout, h, w, b.stride_h, b.stride_w, s, y1, -1, net->act, DL_CONV_ACT);
+    Layer* const ld = b.has_downsample ? layer(i, "wd", b.wd, 1, b.cin, b.cout, h, w, b.stride_h, b.stride_w, s, sc, -1, 0, 0) : nullptr;
+    Layer* const l2 = layer(i, "w2", b.w2, 9, b.cout, b.cout, ho, wo, 1, 1, y1, y2, ld ? sc : s, net->act, DL_CONV_ADD | DL_CONV_ACT);
+    for (Layer* l : {l1, l2, ld}) {
+      if (!l || l->kind == kDirect) continue;
+      l->prepared = p.prepared_bytes;
+      p.prepared_bytes += half ? align_up((size_t)l->taps * l->cout * l->cin * 2) : dl_wino_weights_floats(l->cout, l->cin) * sizeof(float);
+    }
+    s = y2; h = ho; w = wo;
   }
+  p.last_slot = s; p.last_hw = h * w;
   size_t off = 0;
   auto carve = [&](size_t bytes) { const size_t at = off; off += align_up(bytes); return at; };
   for (int i = 0; i < 4; ++i) p.slot_off[i] = carve(p.slot_bytes[i]);
@@ -147,13 +186,59 @@ int at_layer(const char* who, const char* what, int block, int rc) {
   return dl_fail(rc, "%s: %s: %s", who, what, inner);
 }
 
-int pose_forward(const char* who, const dl_pose_net* net, const PosePlan& p, const void* prepared, const float* image_prev, int64_t prev_ss,
+int dtype_check(const char* who, int dtype) {
+  if (dtype != DL_DTYPE_F16 && dtype != DL_DTYPE_BF16)
+    return dl_fail(DL_ERR_UNSUPPORTED, "%s: dtype=%d is not served (1 DL_DTYPE_F16, 2 DL_DTYPE_BF16; fp32 is the family without _h)", who, dtype);
+  return DL_OK;
+}
+
+// dl_pose_net_prepared_bytes / _workspace_bytes (dtype DL_DTYPE_F32) and their _h forms: 0 when the network is refused
+size_t pose_sizes(const char* who, const dl_pose_net* net, int dtype, int B, int H, int W, bool workspace) {
+  if (pose_check(who, net, B, H, W)) return 0;
+  const PosePlan p = pose_plan(net, dtype, B, H, W);
+  return workspace ? p.total : p.prepared_bytes;
+}
+
+// dl_pose_net_prepare (dtype DL_DTYPE_F32: dl_wino_weights_batch_f32, forward set only, DL_WINO_BATCH layers per launch) and
+// dl_pose_net_prepare_h (dl_conv_weights_batch_h, forward layout only, DL_CONVH_BATCH per launch): every record that has a range of
+// `prepared` gets it filled from its parameter
+int pose_prepare(const char* who, const dl_pose_net* net, int dtype, int B, int H, int W, void* prepared, dl_stream stream) {
+  if (int rc = pose_check(who, net, B, H, W)) return rc;
+  if (!prepared || ((uintptr_t)prepared & (kAlign - 1))) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: prepared must be a 256-byte aligned buffer", who);
+  const PosePlan p = pose_plan(net, dtype, B, H, W);
+  const bool half = dtype != DL_DTYPE_F32;
+  dl_wino_layer wino[DL_WINO_BATCH];
+  dl_convh_layer convh[DL_CONVH_BATCH];
+  int n = 0;
+  auto flush = [&]() {
+    const int m = n;
+    n = 0;
+    if (!m) return (int)DL_OK;
+    if (half) return at_layer(who, "half-precision weights", -1, dl_conv_weights_batch_h(convh, m, dtype, stream));
+    return at_layer(who, "Winograd weights", -1, dl_wino_weights_batch_f32(wino, m, stream));
+  };
+  for (int i = 0; i < p.n_layers; ++i) {
+    const Layer& l = p.layers[i];
+    if (l.prepared == kNone) continue;
+    char* const u = (char*)prepared + l.prepared;
+    if (half) convh[n++] = dl_convh_layer{l.weight, u, nullptr, l.cout, l.taps, l.cin};
+    else wino[n++] = dl_wino_layer{l.weight, (float*)u, nullptr, l.cout, l.cin};
+    if (n == (half ? DL_CONVH_BATCH : DL_WINO_BATCH))
+      if (int rc = flush()) return rc;
+  }
+  return flush();
+}
+
+// The walk: in half precision what the fp32 one does with the trunk on dl_conv2d_nhwc_h and the pooling writing the storage type (the
+// Python path pools in fp32 and casts: the same bits); conv1, the pooled feature, the heads and T are fp32 in both.
+int pose_forward(const char* who, const dl_pose_net* net, int dtype, const PosePlan& p, const void* prepared, const float* image_prev, int64_t prev_ss,
                  const float* image_cur, int64_t cur_ss, int B, int H, int W, void* workspace, float* translation, float* quaternion, float* T,
                  dl_stream stream) {
   char* const ws = (char*)workspace;
-  float* slot[4];
-  for (int i = 0; i < 4; ++i) slot[i] = (float*)(ws + p.slot_off[i]);
+  void* slot[4];
+  for (int i = 0; i < 4; ++i) slot[i] = ws + p.slot_off[i];
   void* const split_ws = p.split_bytes ? (void*)(ws + p.split_off) : nullptr;
+  const bool half = dtype != DL_DTYPE_F32;
   const int act = net->act;
   hipStream_t st = (hipStream_t)stream;
   // 1. the transposing gather (x.permute(0, 2, 3, 1).contiguous() of the stacked pair)
@@ -161,40 +246,40 @@ int pose_forward(const char* who, const dl_pose_net* net, const PosePlan& p, con
   hipLaunchKernelGGL(k_interleave_pair, dim3((total + DL_BLOCK - 1) / DL_BLOCK), dim3(DL_BLOCK), 0, st, (const uint32_t*)image_prev, (size_t)prev_ss,
                      (const uint32_t*)image_cur, (size_t)cur_ss, (uint32_t)(H * W), total, (u32x4i*)slot[0]);
   if (int rc = dl_check_launch(who)) return rc;
-  // 2. conv1 (3x3, stride (1,2)) + activation, 3. the pooling
-  if (int rc = at_layer(who, "conv1", -1, dl_conv2d_nhwc_f32(slot[0], net->conv1_w, slot[1], nullptr, nullptr, B, H, W, 8, 64, 3, 1, 2, 0, act, DL_CONV_ACT, stream)))
+  // 2. conv1 (3x3, stride (1,2)) + activation in fp32, 3. the pooling: fp32 with its window plane, or fp32 -> half
+  if (int rc = at_layer(who, "conv1", -1, dl_conv2d_nhwc_f32((const float*)slot[0], net->conv1_w, (float*)slot[1], nullptr, nullptr, B, H, W, 8, 64, 3, 1, 2,
+                                                            0, act, DL_CONV_ACT, stream)))
     return rc;
-  if (int rc = at_layer(who, "pooling", -1, dl_pool3x3s12_nhwc_fwd(slot[1], B, H, W / 2, 64, slot[2], (int8_t*)(ws + p.win_off), stream))) return rc;
+  if (int rc = at_layer(who, "pooling", -1, half ? dl_pool3x3s12_nhwc_fwd_h((const float*)slot[1], B, H, W / 2, 64, dtype, slot[2], stream)
+                                                 : dl_pool3x3s12_nhwc_fwd((const float*)slot[1], B, H, W / 2, 64, (float*)slot[2], (int8_t*)(ws + p.win_off), stream)))
+    return rc;
   // 4. the residual blocks
-  const float* u = (const float*)prepared;
-  int s = 2, h = H, w = W / 4;
-  for (int i = 0; i < net->n_blocks; ++i) {
-    const dl_pose_block& b = net->blocks[i];
-    const int ho = ceil_div(h, b.stride_h), wo = ceil_div(w, b.stride_w);
-    const float* x = slot[s];
-    float *y1 = slot[(s + 1) & 3], *sc = slot[(s + 2) & 3], *y2 = slot[(s + 3) & 3];
-    int rc;
-    if (runs_wino(b.stride_h, b.stride_w)) {
-      rc = dl_wino_conv3x3_nhwc_f32(x, u, y1, nullptr, nullptr, B, h, w, b.cin, b.cout, act, DL_CONV_ACT, split_ws, stream);
-      u += dl_wino_weights_floats(b.cout, b.cin);
-    } else {
-      rc = dl_conv2d_nhwc_f32(x, b.w1, y1, nullptr, nullptr, B, h, w, b.cin, b.cout, 3, b.stride_h, b.stride_w, 0, act, DL_CONV_ACT, stream);
+  for (int i = 0; i < p.n_layers; ++i) {
+    const Layer& l = p.layers[i];
+    const void* x = slot[l.in];
+    void* y = slot[l.out];
+    const void* add = l.add >= 0 ? slot[l.add] : nullptr;
+    const void* u = l.prepared == kNone ? nullptr : (const char*)prepared + l.prepared;
+    const int ks = l.taps == 9 ? 3 : 1;
+    int rc = DL_OK;
+    switch (l.kind) {
+      case kWino:
+        rc = dl_wino_conv3x3_nhwc_f32((const float*)x, (const float*)u, (float*)y, (const float*)add, nullptr, B, l.h, l.w, l.cin, l.cout, l.act, l.epilogue, split_ws, stream);
+        break;
+      case kDirect:
+        rc = dl_conv2d_nhwc_f32((const float*)x, l.weight, (float*)y, (const float*)add, nullptr, B, l.h, l.w, l.cin, l.cout, ks, l.sh, l.sw, 0, l.act, l.epilogue, stream);
+        break;
+      case kHalf:
+        rc = dl_conv2d_nhwc_h(x, u, y, add, nullptr, B, l.h, l.w, l.cin, l.cout, ks, l.sh, l.sw, 0, dtype, l.act, l.epilogue, stream);
+        break;
     }
-    if ((rc = at_layer(who, "w1", i, rc))) return rc;
-    const float* shortcut = x;
-    if (b.has_downsample) {
-      if ((rc = at_layer(who, "wd", i, dl_conv2d_nhwc_f32(x, b.wd, sc, nullptr, nullptr, B, h, w, b.cin, b.cout, 1, b.stride_h, b.stride_w, 0, 0, 0, stream))))
-        return rc;
-      shortcut = sc;
-    }
-    rc = dl_wino_conv3x3_nhwc_f32(y1, u, y2, shortcut, nullptr, B, ho, wo, b.cout, b.cout, act, DL_CONV_ADD | DL_CONV_ACT, split_ws, stream);
-    u += dl_wino_weights_floats(b.cout, b.cout);
-    if ((rc = at_layer(who, "w2", i, rc))) return rc;
-    s = (s + 3) & 3; h = ho; w = wo;
+    if ((rc = at_layer(who, l.name, l.block, rc))) return rc;
   }
-  // 5. global average pooling, 6. fc + heads + the whole-batch quaternion norm, 7. quaternion -> T
+  // 5. global average pooling to the fp32 feature, 6. fc + heads + the whole-batch quaternion norm, 7. quaternion -> T
   float* feat = (float*)(ws + p.feat_off);
-  if (int rc = at_layer(who, "pooled feature", -1, dl_mean_hw_nhwc_f32(slot[s], B, h * w, net->F, feat, stream))) return rc;
+  if (int rc = at_layer(who, "pooled feature", -1, half ? dl_mean_hw_nhwc_h(slot[p.last_slot], B, p.last_hw, net->F, dtype, feat, stream)
+                                                        : dl_mean_hw_nhwc_f32((const float*)slot[p.last_slot], B, p.last_hw, net->F, feat, stream)))
+    return rc;
   if (int rc = at_layer(who, "heads", -1, dl_heads_fwd(feat, &net->heads, B, net->F, net->R, net->Hd, act, (float*)(ws + p.a1_off), (float*)(ws + p.a2_off),
                                                         (float*)(ws + p.rot_off), translation, quaternion, (float*)(ws + p.norm_off), stream)))
     return rc;
@@ -214,269 +299,147 @@ int forward_args(const char* who, const void* prepared, const float* image_prev,
   return DL_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The same walk with the trunk in half precision (the *_h entry points): what ResNetModified.pooled_features_drop does inside
-// torch.autocast in eval mode -- fp32 interleave and conv1, the pooling that writes half precision (the Python path pools in fp32 and
-// casts: the same bits), every trunk layer on dl_conv2d_nhwc_h (one kernel family, so no per-shape routing to mirror), the fp32 pooled
-// feature from dl_mean_hw_nhwc_h, fp32 heads.  The prepared buffer holds w_fwd [taps][K][C] of every trunk convolution, in weight order
-// (w1, w2, wd per block), each at a 256-byte boundary; conv1 and the heads read the fp32 parameters.
-int dtype_check(const char* who, int dtype) {
-  if (dtype != DL_DTYPE_F16 && dtype != DL_DTYPE_BF16)
-    return dl_fail(DL_ERR_UNSUPPORTED, "%s: dtype=%d is not served (1 DL_DTYPE_F16, 2 DL_DTYPE_BF16; fp32 is the family without _h)", who, dtype);
-  return DL_OK;
-}
-
-inline size_t w_fwd_bytes(int taps, int k, int c) { return align_up((size_t)taps * k * c * 2); }
-
-// Four rotating slots as in the fp32 plan: the two stem slots hold fp32 (and later whatever half tensor a block puts there), everything
-// behind the pooling is half.  No fp32 pooled map, no window plane, no split-K scratch.
-PosePlan pose_plan_h(const dl_pose_net* net, int B, int H, int W) {
-  PosePlan p;
-  memset(&p, 0, sizeof(p));
-  auto hold = [&](int slot, size_t bytes) { if (bytes > p.slot_bytes[slot]) p.slot_bytes[slot] = bytes; };
-  hold(0, (size_t)B * H * W * 8 * 4);
-  hold(1, (size_t)B * H * (W / 2) * 64 * 4);
-  hold(2, (size_t)B * H * (W / 4) * 64 * 2);
-  int s = 2, h = H, w = W / 4;
-  for (int i = 0; i < net->n_blocks; ++i) {
-    const dl_pose_block& b = net->blocks[i];
-    const int ho = ceil_div(h, b.stride_h), wo = ceil_div(w, b.stride_w);
-    const size_t out = (size_t)B * ho * wo * b.cout * 2;
-    hold((s + 1) & 3, out);
-    if (b.has_downsample) hold((s + 2) & 3, out);
-    hold((s + 3) & 3, out);
-    p.prepared_bytes += w_fwd_bytes(9, b.cout, b.cin) + w_fwd_bytes(9, b.cout, b.cout) + (b.has_downsample ? w_fwd_bytes(1, b.cout, b.cin) : 0);
-    s = (s + 3) & 3; h = ho; w = wo;
-  }
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { const size_t at = off; off += align_up(bytes); return at; };
-  for (int i = 0; i < 4; ++i) p.slot_off[i] = carve(p.slot_bytes[i]);
-  p.feat_off = carve((size_t)B * net->F * 4);
-  p.a1_off = carve((size_t)B * net->R * 4);
-  p.a2_off = carve((size_t)B * 2 * net->Hd * 4);
-  p.rot_off = carve((size_t)B * 4 * 4);
-  p.norm_off = carve(4);
-  p.total = off;
-  return p;
-}
-
-int pose_forward_h(const char* who, const dl_pose_net* net, int dtype, const PosePlan& p, const void* prepared, const float* image_prev, int64_t prev_ss,
-                   const float* image_cur, int64_t cur_ss, int B, int H, int W, void* workspace, float* translation, float* quaternion, float* T,
-                   dl_stream stream) {
-  char* const ws = (char*)workspace;
-  void* slot[4];
-  for (int i = 0; i < 4; ++i) slot[i] = ws + p.slot_off[i];
-  const int act = net->act;
-  hipStream_t st = (hipStream_t)stream;
-  // 1. the transposing gather, 2. conv1 + activation in fp32, 3. the pooling, fp32 -> half
-  const uint32_t total = (uint32_t)B * H * W;
-  hipLaunchKernelGGL(k_interleave_pair, dim3((total + DL_BLOCK - 1) / DL_BLOCK), dim3(DL_BLOCK), 0, st, (const uint32_t*)image_prev, (size_t)prev_ss,
-                     (const uint32_t*)image_cur, (size_t)cur_ss, (uint32_t)(H * W), total, (u32x4i*)slot[0]);
-  if (int rc = dl_check_launch(who)) return rc;
-  if (int rc = at_layer(who, "conv1", -1, dl_conv2d_nhwc_f32((const float*)slot[0], net->conv1_w, (float*)slot[1], nullptr, nullptr, B, H, W, 8, 64, 3, 1, 2,
-                                                            0, act, DL_CONV_ACT, stream)))
-    return rc;
-  if (int rc = at_layer(who, "pooling", -1, dl_pool3x3s12_nhwc_fwd_h((const float*)slot[1], B, H, W / 2, 64, dtype, slot[2], stream))) return rc;
-  // 4. the residual blocks on the prepared half-precision weights
-  const char* u = (const char*)prepared;
-  int s = 2, h = H, w = W / 4;
-  for (int i = 0; i < net->n_blocks; ++i) {
-    const dl_pose_block& b = net->blocks[i];
-    const int ho = ceil_div(h, b.stride_h), wo = ceil_div(w, b.stride_w);
-    const void* x = slot[s];
-    void *y1 = slot[(s + 1) & 3], *sc = slot[(s + 2) & 3], *y2 = slot[(s + 3) & 3];
-    const char *u1 = u, *u2 = u1 + w_fwd_bytes(9, b.cout, b.cin), *ud = u2 + w_fwd_bytes(9, b.cout, b.cout);
-    u = ud + (b.has_downsample ? w_fwd_bytes(1, b.cout, b.cin) : 0);
-    int rc = dl_conv2d_nhwc_h(x, u1, y1, nullptr, nullptr, B, h, w, b.cin, b.cout, 3, b.stride_h, b.stride_w, 0, dtype, act, DL_CONV_ACT, stream);
-    if ((rc = at_layer(who, "w1", i, rc))) return rc;
-    const void* shortcut = x;
-    if (b.has_downsample) {
-      rc = dl_conv2d_nhwc_h(x, ud, sc, nullptr, nullptr, B, h, w, b.cin, b.cout, 1, b.stride_h, b.stride_w, 0, dtype, 0, 0, stream);
-      if ((rc = at_layer(who, "wd", i, rc))) return rc;
-      shortcut = sc;
-    }
-    rc = dl_conv2d_nhwc_h(y1, u2, y2, shortcut, nullptr, B, ho, wo, b.cout, b.cout, 3, 1, 1, 0, dtype, act, DL_CONV_ADD | DL_CONV_ACT, stream);
-    if ((rc = at_layer(who, "w2", i, rc))) return rc;
-    s = (s + 3) & 3; h = ho; w = wo;
-  }
-  // 5. global average pooling to the fp32 feature, 6. fc + heads + the whole-batch quaternion norm, 7. quaternion -> T: fp32 as ever
-  float* feat = (float*)(ws + p.feat_off);
-  if (int rc = at_layer(who, "pooled feature", -1, dl_mean_hw_nhwc_h(slot[s], B, h * w, net->F, dtype, feat, stream))) return rc;
-  if (int rc = at_layer(who, "heads", -1, dl_heads_fwd(feat, &net->heads, B, net->F, net->R, net->Hd, act, (float*)(ws + p.a1_off), (float*)(ws + p.a2_off),
-                                                        (float*)(ws + p.rot_off), translation, quaternion, (float*)(ws + p.norm_off), stream)))
-    return rc;
-  return at_layer(who, "T", -1, dl_quat_to_T_fwd(translation, quaternion, B, 1e-12f, T, stream));
-}
-
-// dtype DL_DTYPE_F32: the fp32 plan and walk; else the half-precision ones (the streaming calls below serve both families)
-inline PosePlan plan_for(const dl_pose_net* net, int dtype, int B, int H, int W) {
-  return dtype == DL_DTYPE_F32 ? pose_plan(net, B, H, W) : pose_plan_h(net, B, H, W);
-}
-inline int forward_for(const char* who, const dl_pose_net* net, int dtype, const PosePlan& p, const void* prepared, const float* image_prev,
-                       const float* image_cur, int H, int W, void* workspace, float* translation, float* quaternion, float* T, dl_stream stream) {
-  const int64_t ss = (int64_t)4 * H * W;
-  if (dtype == DL_DTYPE_F32) return pose_forward(who, net, p, prepared, image_prev, ss, image_cur, ss, 1, H, W, workspace, translation, quaternion, T, stream);
-  return pose_forward_h(who, net, dtype, p, prepared, image_prev, ss, image_cur, ss, 1, H, W, workspace, translation, quaternion, T, stream);
-}
-
-}  // namespace
-
-/* see include/delora_hip.h */
-extern "C" size_t dl_pose_net_prepared_bytes_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype) {
-  const char* who = "dl_pose_net_prepared_bytes_h";
-  if (dtype_check(who, dtype) || pose_check(who, net, B, H, W)) return 0;
-  return pose_plan_h(net, B, H, W).prepared_bytes;
-}
-
-/* see include/delora_hip.h */
-extern "C" size_t dl_pose_net_workspace_bytes_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype) {
-  const char* who = "dl_pose_net_workspace_bytes_h";
-  if (dtype_check(who, dtype) || pose_check(who, net, B, H, W)) return 0;
-  return pose_plan_h(net, B, H, W).total;
-}
-
-/* see include/delora_hip.h */
-extern "C" int dl_pose_net_prepare_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype, void* prepared, dl_stream stream) {
-  const char* who = "dl_pose_net_prepare_h";
-  if (int rc = dtype_check(who, dtype)) return rc;
-  if (int rc = pose_check(who, net, B, H, W)) return rc;
-  if (!prepared || ((uintptr_t)prepared & (kAlign - 1))) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: prepared must be a 256-byte aligned buffer", who);
-  // every trunk convolution in weight order (w1, w2, wd per block), forward layout only, DL_CONVH_BATCH per launch
-  dl_convh_layer layers[3 * DL_POSE_NET_MAX_BLOCKS];
-  int n = 0;
-  char* u = (char*)prepared;
-  auto put = [&](const float* w, int taps, int k, int c) {
-    layers[n++] = dl_convh_layer{w, u, nullptr, k, taps, c};
-    u += w_fwd_bytes(taps, k, c);
-  };
-  for (int i = 0; i < net->n_blocks; ++i) {
-    const dl_pose_block& b = net->blocks[i];
-    put(b.w1, 9, b.cout, b.cin);
-    put(b.w2, 9, b.cout, b.cout);
-    if (b.has_downsample) put(b.wd, 1, b.cout, b.cin);
-  }
-  for (int i0 = 0; i0 < n; i0 += DL_CONVH_BATCH) {
-    const int m = n - i0 < DL_CONVH_BATCH ? n - i0 : DL_CONVH_BATCH;
-    if (int rc = at_layer(who, "half-precision weights", -1, dl_conv_weights_batch_h(layers + i0, m, dtype, stream))) return rc;
-  }
-  return DL_OK;
-}
-
-/* see include/delora_hip.h */
-extern "C" int dl_pose_net_forward_h(const dl_pose_net* net, const void* prepared, const float* image_prev, int64_t prev_ss, const float* image_cur,
-                                     int64_t cur_ss, int32_t B, int32_t H, int32_t W, int32_t dtype, void* workspace, float* translation,
-                                     float* quaternion, float* T, dl_stream stream) {
-  const char* who = "dl_pose_net_forward_h";
-  if (int rc = dtype_check(who, dtype)) return rc;
+// dl_pose_net_forward (dtype DL_DTYPE_F32) and dl_pose_net_forward_h
+int pose_net_forward(const char* who, const dl_pose_net* net, int dtype, const void* prepared, const float* image_prev, int64_t prev_ss, const float* image_cur,
+                     int64_t cur_ss, int B, int H, int W, void* workspace, float* translation, float* quaternion, float* T, dl_stream stream) {
   if (int rc = pose_check(who, net, B, H, W)) return rc;
   if (int rc = forward_args(who, prepared, image_prev, prev_ss, image_cur, cur_ss, H, W, workspace, translation, quaternion, T)) return rc;
-  const PosePlan p = pose_plan_h(net, B, H, W);
-  return pose_forward_h(who, net, dtype, p, prepared, image_prev, prev_ss, image_cur, cur_ss, B, H, W, workspace, translation, quaternion, T, stream);
+  return pose_forward(who, net, dtype, pose_plan(net, dtype, B, H, W), prepared, image_prev, prev_ss, image_cur, cur_ss, B, H, W, workspace, translation,
+                      quaternion, T, stream);
 }
 
-/* see include/delora_hip.h */
-extern "C" size_t dl_pose_net_prepared_bytes(const dl_pose_net* net, int32_t B, int32_t H, int32_t W) {
-  if (pose_check("dl_pose_net_prepared_bytes", net, B, H, W)) return 0;
-  return pose_plan(net, B, H, W).prepared_bytes;
-}
-
-/* see include/delora_hip.h */
-extern "C" size_t dl_pose_net_workspace_bytes(const dl_pose_net* net, int32_t B, int32_t H, int32_t W) {
-  if (pose_check("dl_pose_net_workspace_bytes", net, B, H, W)) return 0;
-  return pose_plan(net, B, H, W).total;
-}
-
-/* see include/delora_hip.h */
-extern "C" int dl_pose_net_prepare(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, void* prepared, dl_stream stream) {
-  const char* who = "dl_pose_net_prepare";
-  if (int rc = pose_check(who, net, B, H, W)) return rc;
-  if (!prepared || ((uintptr_t)prepared & (kAlign - 1))) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: prepared must be a 256-byte aligned buffer", who);
-  // the Winograd layers in block order (conv1 of the stride-1 blocks, conv2 of every block), DL_WINO_BATCH per launch
-  dl_wino_layer layers[2 * DL_POSE_NET_MAX_BLOCKS];
-  int n = 0;
-  float* u = (float*)prepared;
-  for (int i = 0; i < net->n_blocks; ++i) {
-    const dl_pose_block& b = net->blocks[i];
-    if (runs_wino(b.stride_h, b.stride_w)) {
-      layers[n++] = dl_wino_layer{b.w1, u, nullptr, b.cout, b.cin};
-      u += dl_wino_weights_floats(b.cout, b.cin);
-    }
-    layers[n++] = dl_wino_layer{b.w2, u, nullptr, b.cout, b.cout};
-    u += dl_wino_weights_floats(b.cout, b.cout);
-  }
-  for (int i0 = 0; i0 < n; i0 += DL_WINO_BATCH) {
-    const int m = n - i0 < DL_WINO_BATCH ? n - i0 : DL_WINO_BATCH;
-    if (int rc = at_layer(who, "Winograd weights", -1, dl_wino_weights_batch_f32(layers + i0, m, stream))) return rc;
-  }
-  return DL_OK;
-}
-
-/* see include/delora_hip.h */
-extern "C" int dl_pose_net_forward(const dl_pose_net* net, const void* prepared, const float* image_prev, int64_t prev_ss, const float* image_cur,
-                                   int64_t cur_ss, int32_t B, int32_t H, int32_t W, void* workspace, float* translation, float* quaternion, float* T,
-                                   dl_stream stream) {
-  const char* who = "dl_pose_net_forward";
-  if (int rc = pose_check(who, net, B, H, W)) return rc;
-  if (int rc = forward_args(who, prepared, image_prev, prev_ss, image_cur, cur_ss, H, W, workspace, translation, quaternion, T)) return rc;
-  const PosePlan p = pose_plan(net, B, H, W);
-  return pose_forward(who, net, p, prepared, image_prev, prev_ss, image_cur, cur_ss, B, H, W, workspace, translation, quaternion, T, stream);
-}
-
-// workspace of dl_odometry_push: the forward's workspace (B = 1) | pix2pt [H*W] int32 | the projection's scratch (grows with the scan)
-static int odometry_check(const char* who, const dl_pose_net* net, const dl_sensor* sensor) {
+// workspace of the streaming calls: the forward's workspace (B = 1) | pix2pt [H*W] int32 | the projection's scratch (grows with the scan)
+int odometry_check(const char* who, const dl_pose_net* net, const dl_sensor* sensor) {
   if (!sensor) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null sensor", who);
   if (sensor->H < 2 || sensor->W < 2) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad sensor H=%d W=%d", who, sensor->H, sensor->W);
   return pose_check(who, net, 1, sensor->H, sensor->W);
 }
 
 // dl_odometry_workspace_bytes (dtype DL_DTYPE_F32) and dl_odometry_workspace_bytes_h
-static size_t odometry_workspace(const char* who, const dl_pose_net* net, int dtype, const dl_sensor* sensor, int32_t max_points, int32_t H, int32_t W) {
+size_t odometry_workspace(const char* who, const dl_pose_net* net, int dtype, const dl_sensor* sensor, int32_t max_points, int32_t H, int32_t W) {
   if (odometry_check(who, net, sensor)) return 0;
   if (H != sensor->H || W != sensor->W || max_points < 0) {
     dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: H=%d W=%d must be the sensor's %dx%d, max_points=%d not negative", who, H, W, sensor->H, sensor->W, max_points);
     return 0;
   }
-  return plan_for(net, dtype, 1, H, W).total + align_up((size_t)H * W * 4) + align_up(dl_project_workspace_bytes(1, H, W, max_points, 3));
+  return pose_plan(net, dtype, 1, H, W).total + align_up((size_t)H * W * 4) + align_up(dl_project_workspace_bytes(1, H, W, max_points, 3));
 }
 
-/* see include/delora_hip.h */
+int push_alignment(const char* who, const void* workspace, const float* image_cur, const int32_t* offs) {
+  if (((uintptr_t)workspace & (kAlign - 1))) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: workspace must be 256-byte aligned", who);
+  if (((uintptr_t)image_cur & 3) || ((uintptr_t)offs & 3)) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: image_cur / offs are not 4-byte aligned", who);
+  return DL_OK;
+}
+
+// The body of the four push calls behind odometry_check and the scan's own argument checks: the CSR offsets {0, n} of the single scan,
+// project(pix2pt, scratch) -- the new scan alone into image_cur -- and, from the second scan on, the forward on (image_prev, image_cur).
+template <class Project>
+int odometry_push_body(const char* who, int dtype, const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, int32_t n, int32_t* offs,
+                       const float* image_prev, float* image_cur, void* workspace, float* translation, float* quaternion, float* T, dl_stream stream,
+                       Project project) {
+  const int H = sensor->H, W = sensor->W;
+  const int64_t ss = (int64_t)4 * H * W;
+  if (image_prev)
+    if (int rc = forward_args(who, prepared, image_prev, ss, image_cur, ss, H, W, workspace, translation, quaternion, T)) return rc;
+  const PosePlan p = pose_plan(net, dtype, 1, H, W);
+  char* const ws = (char*)workspace;
+  int32_t* pix2pt = (int32_t*)(ws + p.total);
+  void* project_ws = ws + p.total + align_up((size_t)H * W * 4);
+  hipLaunchKernelGGL(k_single_scan_offsets, dim3(1), dim3(64), 0, (hipStream_t)stream, offs, n);
+  if (int rc = dl_check_launch(who)) return rc;
+  if (int rc = at_layer(who, "projection", -1, project(pix2pt, project_ws))) return rc;
+  if (!image_prev) return DL_OK;
+  return pose_forward(who, net, dtype, p, prepared, image_prev, ss, image_cur, ss, 1, H, W, workspace, translation, quaternion, T, stream);
+}
+
+// dl_odometry_push (dtype DL_DTYPE_F32) and dl_odometry_push_h
+int odometry_push(const char* who, int dtype, const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs,
+                  int32_t n_points, int32_t* offs, const float* image_prev, float* image_cur, void* workspace, float* translation, float* quaternion,
+                  float* T, dl_stream stream) {
+  if (int rc = odometry_check(who, net, sensor)) return rc;
+  if (!offs || !image_cur || !workspace || (!pts && n_points > 0)) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument (pts, offs, image_cur, workspace)", who);
+  if (n_points < 0 || pts_cs < n_points) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad sizes n_points=%d pts_cs=%lld", who, n_points, (long long)pts_cs);
+  if (int rc = push_alignment(who, workspace, image_cur, offs)) return rc;
+  return odometry_push_body(who, dtype, net, prepared, sensor, n_points, offs, image_prev, image_cur, workspace, translation, quaternion, T, stream,
+                            [&](int32_t* pix2pt, void* project_ws) {
+                              return dl_project(pts, pts_cs, n_points, offs, 1, 3, n_points, sensor, image_cur, nullptr, nullptr, nullptr, pix2pt, project_ws,
+                                                nullptr, nullptr, stream);
+                            });
+}
+
+// dl_odometry_push_records (dtype DL_DTYPE_F32) and dl_odometry_push_records_h; the projection's scratch is the key plane alone:
+// dl_odometry_workspace_bytes with max_points = 0
+int odometry_push_records(const char* who, int dtype, const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records,
+                          int32_t n_records, const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur, void* workspace,
+                          float* translation, float* quaternion, float* T, dl_stream stream) {
+  if (int rc = odometry_check(who, net, sensor)) return rc;
+  if (!offs || !image_cur || !workspace || !layout || (!records && n_records > 0))
+    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument (records, layout, offs, image_cur, workspace)", who);
+  if (n_records < 0) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad sizes n_records=%d", who, n_records);
+  if (int rc = push_alignment(who, workspace, image_cur, offs)) return rc;
+  if (int rc = dl_record_layout_check(who, records, layout)) return rc;
+  return odometry_push_body(who, dtype, net, prepared, sensor, n_records, offs, image_prev, image_cur, workspace, translation, quaternion, T, stream,
+                            [&](int32_t* pix2pt, void* project_ws) {
+                              return dl_project_records(records, n_records, layout, offs, 1, n_records, sensor, image_cur, nullptr, pix2pt, project_ws, nullptr,
+                                                        nullptr, stream);
+                            });
+}
+
+}  // namespace
+
+/* The entry points (see include/delora_hip.h): the fp32 family passes DL_DTYPE_F32 to the shared bodies, the _h family checks its dtype first. */
+extern "C" size_t dl_pose_net_prepared_bytes(const dl_pose_net* net, int32_t B, int32_t H, int32_t W) {
+  return pose_sizes("dl_pose_net_prepared_bytes", net, DL_DTYPE_F32, B, H, W, false);
+}
+
+extern "C" size_t dl_pose_net_prepared_bytes_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype) {
+  const char* who = "dl_pose_net_prepared_bytes_h";
+  return dtype_check(who, dtype) ? 0 : pose_sizes(who, net, dtype, B, H, W, false);
+}
+
+extern "C" size_t dl_pose_net_workspace_bytes(const dl_pose_net* net, int32_t B, int32_t H, int32_t W) {
+  return pose_sizes("dl_pose_net_workspace_bytes", net, DL_DTYPE_F32, B, H, W, true);
+}
+
+extern "C" size_t dl_pose_net_workspace_bytes_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype) {
+  const char* who = "dl_pose_net_workspace_bytes_h";
+  return dtype_check(who, dtype) ? 0 : pose_sizes(who, net, dtype, B, H, W, true);
+}
+
+extern "C" int dl_pose_net_prepare(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, void* prepared, dl_stream stream) {
+  return pose_prepare("dl_pose_net_prepare", net, DL_DTYPE_F32, B, H, W, prepared, stream);
+}
+
+extern "C" int dl_pose_net_prepare_h(const dl_pose_net* net, int32_t B, int32_t H, int32_t W, int32_t dtype, void* prepared, dl_stream stream) {
+  const char* who = "dl_pose_net_prepare_h";
+  if (int rc = dtype_check(who, dtype)) return rc;
+  return pose_prepare(who, net, dtype, B, H, W, prepared, stream);
+}
+
+extern "C" int dl_pose_net_forward(const dl_pose_net* net, const void* prepared, const float* image_prev, int64_t prev_ss, const float* image_cur,
+                                   int64_t cur_ss, int32_t B, int32_t H, int32_t W, void* workspace, float* translation, float* quaternion, float* T,
+                                   dl_stream stream) {
+  return pose_net_forward("dl_pose_net_forward", net, DL_DTYPE_F32, prepared, image_prev, prev_ss, image_cur, cur_ss, B, H, W, workspace, translation,
+                          quaternion, T, stream);
+}
+
+extern "C" int dl_pose_net_forward_h(const dl_pose_net* net, const void* prepared, const float* image_prev, int64_t prev_ss, const float* image_cur,
+                                     int64_t cur_ss, int32_t B, int32_t H, int32_t W, int32_t dtype, void* workspace, float* translation,
+                                     float* quaternion, float* T, dl_stream stream) {
+  const char* who = "dl_pose_net_forward_h";
+  if (int rc = dtype_check(who, dtype)) return rc;
+  return pose_net_forward(who, net, dtype, prepared, image_prev, prev_ss, image_cur, cur_ss, B, H, W, workspace, translation, quaternion, T, stream);
+}
+
 extern "C" size_t dl_odometry_workspace_bytes(const dl_pose_net* net, const dl_sensor* sensor, int32_t max_points, int32_t H, int32_t W) {
   return odometry_workspace("dl_odometry_workspace_bytes", net, DL_DTYPE_F32, sensor, max_points, H, W);
 }
 
-/* see include/delora_hip.h */
 extern "C" size_t dl_odometry_workspace_bytes_h(const dl_pose_net* net, const dl_sensor* sensor, int32_t max_points, int32_t H, int32_t W, int32_t dtype) {
   const char* who = "dl_odometry_workspace_bytes_h";
-  if (dtype_check(who, dtype)) return 0;
-  return odometry_workspace(who, net, dtype, sensor, max_points, H, W);
+  return dtype_check(who, dtype) ? 0 : odometry_workspace(who, net, dtype, sensor, max_points, H, W);
 }
 
-// dl_odometry_push (dtype DL_DTYPE_F32) and dl_odometry_push_h
-static int odometry_push(const char* who, int dtype, const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs,
-                         int32_t n_points, int32_t* offs, const float* image_prev, float* image_cur, void* workspace, float* translation,
-                         float* quaternion, float* T, dl_stream stream) {
-  if (int rc = odometry_check(who, net, sensor)) return rc;
-  const int H = sensor->H, W = sensor->W;
-  if (!offs || !image_cur || !workspace || (!pts && n_points > 0)) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument (pts, offs, image_cur, workspace)", who);
-  if (n_points < 0 || pts_cs < n_points) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad sizes n_points=%d pts_cs=%lld", who, n_points, (long long)pts_cs);
-  if (((uintptr_t)workspace & (kAlign - 1))) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: workspace must be 256-byte aligned", who);
-  if (((uintptr_t)image_cur & 3) || ((uintptr_t)offs & 3)) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: image_cur / offs are not 4-byte aligned", who);
-  if (image_prev)
-    if (int rc = forward_args(who, prepared, image_prev, (int64_t)4 * H * W, image_cur, (int64_t)4 * H * W, H, W, workspace, translation, quaternion, T)) return rc;
-  const PosePlan p = plan_for(net, dtype, 1, H, W);
-  char* const ws = (char*)workspace;
-  int32_t* pix2pt = (int32_t*)(ws + p.total);
-  void* project_ws = ws + p.total + align_up((size_t)H * W * 4);
-  hipLaunchKernelGGL(k_single_scan_offsets, dim3(1), dim3(64), 0, (hipStream_t)stream, offs, n_points);
-  if (int rc = dl_check_launch(who)) return rc;
-  if (int rc = at_layer(who, "projection", -1, dl_project(pts, pts_cs, n_points, offs, 1, 3, n_points, sensor, image_cur, nullptr, nullptr, nullptr, pix2pt,
-                                                          project_ws, nullptr, nullptr, stream)))
-    return rc;
-  if (!image_prev) return DL_OK;
-  return forward_for(who, net, dtype, p, prepared, image_prev, image_cur, H, W, workspace, translation, quaternion, T, stream);
-}
-
-/* see include/delora_hip.h */
 extern "C" int dl_odometry_push(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs, int32_t n_points,
                                 int32_t* offs, const float* image_prev, float* image_cur, void* workspace, float* translation, float* quaternion,
                                 float* T, dl_stream stream) {
@@ -484,7 +447,6 @@ extern "C" int dl_odometry_push(const dl_pose_net* net, const void* prepared, co
                        quaternion, T, stream);
 }
 
-/* see include/delora_hip.h */
 extern "C" int dl_odometry_push_h(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const float* pts, int64_t pts_cs, int32_t n_points,
                                   int32_t* offs, const float* image_prev, float* image_cur, int32_t dtype, void* workspace, float* translation,
                                   float* quaternion, float* T, dl_stream stream) {
@@ -493,35 +455,6 @@ extern "C" int dl_odometry_push_h(const dl_pose_net* net, const void* prepared, 
   return odometry_push(who, dtype, net, prepared, sensor, pts, pts_cs, n_points, offs, image_prev, image_cur, workspace, translation, quaternion, T, stream);
 }
 
-// dl_odometry_push_records (dtype DL_DTYPE_F32) and dl_odometry_push_records_h
-static int odometry_push_records(const char* who, int dtype, const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records,
-                                 int32_t n_records, const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur,
-                                 void* workspace, float* translation, float* quaternion, float* T, dl_stream stream) {
-  if (int rc = odometry_check(who, net, sensor)) return rc;
-  const int H = sensor->H, W = sensor->W;
-  if (!offs || !image_cur || !workspace || !layout || (!records && n_records > 0))
-    return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: null pointer argument (records, layout, offs, image_cur, workspace)", who);
-  if (n_records < 0) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: bad sizes n_records=%d", who, n_records);
-  if (((uintptr_t)workspace & (kAlign - 1))) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: workspace must be 256-byte aligned", who);
-  if (((uintptr_t)image_cur & 3) || ((uintptr_t)offs & 3)) return dl_fail(DL_ERR_INVALID_ARGUMENT, "%s: image_cur / offs are not 4-byte aligned", who);
-  if (int rc = dl_record_layout_check(who, records, layout)) return rc;
-  if (image_prev)
-    if (int rc = forward_args(who, prepared, image_prev, (int64_t)4 * H * W, image_cur, (int64_t)4 * H * W, H, W, workspace, translation, quaternion, T)) return rc;
-  // workspace: the forward's (B = 1) | pix2pt [H*W] int32 | the key plane -- dl_odometry_workspace_bytes with max_points = 0
-  const PosePlan p = plan_for(net, dtype, 1, H, W);
-  char* const ws = (char*)workspace;
-  int32_t* pix2pt = (int32_t*)(ws + p.total);
-  void* project_ws = ws + p.total + align_up((size_t)H * W * 4);
-  hipLaunchKernelGGL(k_single_scan_offsets, dim3(1), dim3(64), 0, (hipStream_t)stream, offs, n_records);
-  if (int rc = dl_check_launch(who)) return rc;
-  if (int rc = at_layer(who, "projection", -1, dl_project_records(records, n_records, layout, offs, 1, n_records, sensor, image_cur, nullptr, pix2pt,
-                                                                  project_ws, nullptr, nullptr, stream)))
-    return rc;
-  if (!image_prev) return DL_OK;
-  return forward_for(who, net, dtype, p, prepared, image_prev, image_cur, H, W, workspace, translation, quaternion, T, stream);
-}
-
-/* see include/delora_hip.h */
 extern "C" int dl_odometry_push_records(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records, int32_t n_records,
                                         const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur, void* workspace,
                                         float* translation, float* quaternion, float* T, dl_stream stream) {
@@ -529,7 +462,6 @@ extern "C" int dl_odometry_push_records(const dl_pose_net* net, const void* prep
                                workspace, translation, quaternion, T, stream);
 }
 
-/* see include/delora_hip.h */
 extern "C" int dl_odometry_push_records_h(const dl_pose_net* net, const void* prepared, const dl_sensor* sensor, const void* records, int32_t n_records,
                                           const dl_record_layout* layout, int32_t* offs, const float* image_prev, float* image_cur, int32_t dtype,
                                           void* workspace, float* translation, float* quaternion, float* T, dl_stream stream) {

@@ -10,11 +10,43 @@ import torch
 from delora_amd import _lib, geometry
 from delora_amd.deploy import native_infer
 from delora_amd.ros_utils import odometry
-from tests.test_native_infer_host import BLOCKS, F, HD, R, _cpu_model, dummy_address, make_net, up
+from tests.test_native_infer_host import BLOCKS, F, HD, R, _cpu_model, dummy_address, make_net, plan_restated, up
 
 UNSUPPORTED, INVALID = -3, -1
 F16, BF16 = 1, 2
 SHAPES = ((1, 16, 128), (2, 16, 128), (3, 5, 36), (1, 64, 720), (8, 64, 2048))
+# the reference network and four others that leave the slot rotation at every phase: one block, an end on a strided block, five blocks
+# (the rotation past a full turn), a strided first block
+BLOCK_LISTS = (BLOCKS, BLOCKS[:1], BLOCKS[:3], BLOCKS[:5], ((64, 128, (2, 2), True), (128, 128, (1, 1), False)))
+
+
+def prepared_restated_h(blocks):
+    """Every trunk convolution as w_fwd [taps][K][C] in 2-byte elements, each array rounded up to 256 bytes."""
+    return sum(up(9 * cout * cin * 2) + up(9 * cout * cout * 2) + (up(1 * cout * cin * 2) if has_ds else 0) for (cin, cout, _, has_ds) in blocks)
+
+
+def plan_restated_h(blocks, B, H, W, sizes=(F, R, HD)):
+    """Workspace bytes of the half-precision family: the liveness walk of ``plan_restated`` (tests/test_native_infer_host.py) with the
+    interleaved input and conv1's output (slots 0 and 1) in 4-byte elements, the pooled map and every block tensor in 2-byte elements, no
+    window plane and no split-K scratch; then the fp32 pooled feature and the heads' four saved tensors; every part rounded up to 256."""
+    slots = [0, 0, 0, 0]
+
+    def hold(s, nbytes):
+        slots[s % 4] = max(slots[s % 4], nbytes)
+
+    hold(0, 4 * B * H * W * 8)
+    hold(1, 4 * B * H * (W // 2) * 64)
+    hold(2, 2 * B * H * (W // 4) * 64)
+    s, h, w = 2, H, W // 4
+    for (cin, cout, (sh, sw), has_ds) in blocks:
+        ho, wo = -(-h // sh), -(-w // sw)
+        hold(s + 1, 2 * B * ho * wo * cout)
+        if has_ds:
+            hold(s + 2, 2 * B * ho * wo * cout)
+        hold(s + 3, 2 * B * ho * wo * cout)
+        s, h, w = s + 3, ho, wo
+    f, r, hd = sizes
+    return sum(up(p) for p in slots + [4 * B * f, 4 * B * r, 4 * B * 2 * hd, 4 * B * 4, 4])
 
 
 def test_abi_version_is_unchanged():
@@ -28,9 +60,7 @@ def test_prepared_bytes_are_the_trunks_forward_weights_in_half_precision(B, H, W
     block, the 1x1 shortcut of the three strided ones.  The image size does not enter."""
     lib = _lib.load()
     _, p = make_net()
-    want = 0
-    for (cin, cout, _, has_ds) in BLOCKS:
-        want += up(9 * cout * cin * 2) + up(9 * cout * cout * 2) + (up(1 * cout * cin * 2) if has_ds else 0)
+    want = prepared_restated_h(BLOCKS)
     assert lib.dl_pose_net_prepared_bytes_h(p, B, H, W, dtype) == want, lib.dl_last_error()
     # by hand for the reference network: sixteen 3x3 layers and three 1x1 shortcuts, all multiples of 256 bytes already
     by_hand = 2 * (9 * (4 * 64 * 64 + 128 * 64 + 3 * 128 * 128 + 256 * 128 + 3 * 256 * 256 + 512 * 256 + 3 * 512 * 512)
@@ -51,6 +81,30 @@ def test_workspace_is_smaller_than_the_fp32_one(dtype):
     for n in (0, 1000):
         want = lib.dl_pose_net_workspace_bytes_h(p, 1, 64, 720, dtype) + up(64 * 720 * 4) + up(lib.dl_project_workspace_bytes(1, 64, 720, n, 3))
         assert lib.dl_odometry_workspace_bytes_h(p, ctypes.byref(sensor.struct), n, 64, 720, dtype) == want
+
+
+@pytest.mark.parametrize("dtype", (F16, BF16))
+@pytest.mark.parametrize("B,H,W", SHAPES)
+def test_workspace_equals_the_restated_half_plan(B, H, W, dtype):
+    lib = _lib.load()
+    _, p = make_net()
+    assert lib.dl_pose_net_workspace_bytes_h(p, B, H, W, dtype) == plan_restated_h(BLOCKS, B, H, W), lib.dl_last_error()
+
+
+@pytest.mark.parametrize("blocks", BLOCK_LISTS[1:], ids=("one", "three", "five", "strided_first"))
+def test_other_block_lists_equal_the_restated_plans_in_both_families(blocks):
+    """Shorter networks (F = the last block's channels) start and end the slot rotation at other phases: both workspace restatements,
+    the fp32 prepared bytes and the half prepared bytes, at every shape and in both storage types."""
+    lib = _lib.load()
+    sizes = (blocks[-1][1], R, HD)
+    _, p = make_net(blocks, sizes=sizes)
+    for (B, H, W) in SHAPES:
+        ws, prepared = plan_restated(lib, blocks, B, H, W, sizes)
+        assert lib.dl_pose_net_workspace_bytes(p, B, H, W) == ws, lib.dl_last_error()
+        assert lib.dl_pose_net_prepared_bytes(p, B, H, W) == prepared, lib.dl_last_error()
+        for dtype in (F16, BF16):
+            assert lib.dl_pose_net_workspace_bytes_h(p, B, H, W, dtype) == plan_restated_h(blocks, B, H, W, sizes), lib.dl_last_error()
+            assert lib.dl_pose_net_prepared_bytes_h(p, B, H, W, dtype) == prepared_restated_h(blocks), lib.dl_last_error()
 
 
 def _calls(lib, p, dtype, B=1, H=16, W=128, prepared=None, workspace=None, sensor=None):
